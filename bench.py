@@ -2,6 +2,7 @@
 """bench.py -- EM iterations/sec of the pLSA hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3] [--schedule fused|materialised] [--topics 64]
+                    [--dump-outputs DIR] [--full]
     python bench.py --gpus 8 --config 4        BASELINE configs[3]: the 32-member ensemble on the 20NG shape over 8 GPUs
 
 A "step" is one EM iteration (E-step + M-step, plus the log-likelihood test at the reference's
@@ -13,7 +14,12 @@ uses: the member's topics go into the engine's device stack and enstop_amd.distr
 (plsa_comm_allgather_stack: one grouped ncclAllGather from the C ABI + one copy to pinned host memory; no
 PyTorch in the process).  `value` is the whole-job aggregate: (N * K) EM iterations / max-over-ranks wall time.
 
-`ensemble` (every N): a MEASURED ensemble through the product's own call -- enstop_amd.ensemble_of_topics on the
+A plain run sets up, runs W untimed iterations, times ONE region of exactly K iterations from the initial factors (barrier +
+synchronize around it, the engine's per-kernel events off, max over ranks), writes the fit's outputs when --dump-outputs is
+given (dump_outputs) and prints the line: `value` = (N * K) / that region's wall time, `ms_per_step` = the region / K.  Every
+other leg below runs only with --full, which keeps the same headline region and adds the rest.
+
+`ensemble` (every N, --full): a MEASURED ensemble through the product's own call -- enstop_amd.ensemble_of_topics on the
 host copy of the same corpus, four members per rank (after one untimed warm-up member), 50 EM iterations each: upload, bootstrap row gather, CSC /
 item build (+ boundary tuning), MT19937 initialisation on the device, fit, stack, gather -- wall clock between
 two barriers, max over ranks -> `ensemble.fits_per_min`, with each rank's fit / gather / RCCL-init seconds.
@@ -28,11 +34,11 @@ mode for single-GPU boxes (ranks share the GPU, host-file exchange) and says so 
 Inputs are generated in HBM before the timed region (plsa_generate_synthetic); factors are
 initialised on the host exactly as plsa_init does and uploaded before the timed region.
 
-`value` is the MEDIAN of three back-to-back timed regions of exactly K iterations each (every region bracketed by
-barrier + synchronize, max over ranks); all three are listed in `timed_regions` (round 3: one of eight fresh
-processes ended 6 % low after an unlucky boundary tuning -- one region must not become the driver's number).
+--full adds three further regions of exactly K iterations with the per-kernel HIP events on, listed in `timed_regions`;
+the per-kernel figures come from their median (round 3: one of eight fresh processes ended 6 % low after an unlucky
+boundary tuning -- compare `value` with them).
 
-Extra objects in the JSON line:
+Extra objects of a --full run (the compact line printed, the full object in --full-json):
   roofline      the per-nnz materialising E-step kernel (plsa.py:39-107; the kernel the north_star
                 roofline target names): algorithmic bytes (SURVEY.md section 8d / DESIGN.md) / average
                 launch duration, HIP events on the engine's stream over a second timed leg that runs
@@ -134,13 +140,22 @@ def init_factors(n, m, k, seed):
     return U.astype(np.float32), V.astype(np.float32)
 
 
+def host_threads():
+    """CPUs this process may use: OMP_NUM_THREADS when set, else its CPU affinity.  os.cpu_count() counts the whole host, and
+    a thread pool larger than the CPUs granted only slows the port down."""
+    try:
+        return max(1, int(os.environ["OMP_NUM_THREADS"].split(",")[0]))
+    except (KeyError, ValueError):
+        return len(os.sched_getaffinity(0))
+
+
 def cpu_baseline(eng, cfg, k, budget_cells=1.2e9, iters=3, whole=False):
-    """Reference-structure CPU port (the only place of this script that touches oracle/), all host cores.
+    """Reference-structure CPU port (the only place of this script that touches oracle/), on host_threads() threads.
     whole=False: on the first rows of the corpus resident on `eng`, bounded to ~budget_cells cells per
     iteration, scaled by the nnz fraction ("sampled": true).  whole=True: on the whole corpus, no scaling."""
     from oracle.plsa_oracle import Oracle
     o = Oracle(fast=True)
-    cores = os.cpu_count() or 1
+    cores = host_threads()
     o.set_threads(cores)
     A = eng.download_active_csr()
     n, m = A.shape
@@ -533,10 +548,11 @@ def reference_arithmetic_leg(eng, seed):
 
 
 def compact_line(out, full_path=None):
-    """The ONE JSON line of a default run: the contract keys, `roofline` (north-star kernel + `timed_loop` = the dominant
-    kernel of the loop `value` times), `cpu_baseline`, every other BASELINE configuration and the ensemble legs as one
-    short object each -- sized to fit the 2000-character tail the driver keeps.  Everything else (per-kernel tables,
-    register counts, counter traffic, schedules) is in the full object (`full`, --full-json / --full)."""
+    """The ONE JSON line of a run: the contract keys and `config`; with --full also `roofline` (north-star kernel +
+    `timed_loop` = the dominant kernel of the loop `value` times), `cpu_baseline`, every other BASELINE configuration and
+    the ensemble legs as one short object each -- sized to fit the 2000-character tail the driver keeps.  Everything else
+    (per-kernel tables, register counts, counter traffic, schedules) is in the full object (`full`, --full-json;
+    --full-object prints it)."""
     line = _pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                  "vs_baseline", "dtype", "data")
     c = out.get("config", {})
@@ -544,16 +560,18 @@ def compact_line(out, full_path=None):
                       "corpus": "topical" if str(c.get("corpus", "")).startswith("topical") else "independent Zipf tokens (SURVEY 8d)",
                       "nnz": c.get("nnz"), "k": c.get("k"), "schedule": c.get("schedule"),
                       "parallelism": str(c.get("parallelism", ""))[:60]}
-    r = out.get("roofline") or {}
-    line["roofline"] = _pick(r, "kernel", "leg", "bound", "achieved", "peak", "unit", "frac", "traffic")
-    line["roofline"]["avg_ms"] = r.get("avg_launch_ms")
-    if "timed_loop" in r:
-        line["roofline"]["timed_loop"] = r["timed_loop"]
+    r = out.get("roofline")
+    if r:
+        line["roofline"] = _pick(r, "kernel", "leg", "bound", "achieved", "peak", "unit", "frac", "traffic")
+        line["roofline"]["avg_ms"] = r.get("avg_launch_ms")
+        if "timed_loop" in r:
+            line["roofline"]["timed_loop"] = r["timed_loop"]
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         line["cpu_baseline"] = _pick(cb, "value", "unit", "cores", "kind", "sampled")
         line["cpu_baseline"]["sample"] = str(cb.get("sample", ""))[:90]
-    line["timed_regions"] = [t.get("value") for t in out.get("timed_regions", [])]
+    if "timed_regions" in out:
+        line["timed_regions"] = [t.get("value") for t in out["timed_regions"]]
     line["rccl_ranks"] = out.get("rccl_ranks", 0)
     line["exchange"] = str(out.get("exchange", ""))[:60]
     oc = out.get("other_configs")
@@ -588,6 +606,33 @@ def compact_line(out, full_path=None):
     return line
 
 
+DUMP_SAMPLE_SEED = 20240601        # --dump-outputs: the rows / columns kept of a matrix above its share of the 64 MB
+DUMP_SHARE_BYTES = {"doc_topic": 24_000_000, "topic_word": 36_000_000, "topic_stack": 36_000_000}
+
+
+def dump_outputs(path, eng, ll_trace, stack):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the document-topic matrix P(z|d)
+    (`doc_topic`), the topic-word matrix P(w|z) (`topic_word`; with N > 1 the gathered stack of every rank's topics,
+    `topic_stack`, instead) and the log-likelihood trace of the fit -- as float32 .npy files.  A matrix larger than its share of
+    the 64 MB keeps a fixed, seeded sample of its rows (doc_topic) or columns (the topic matrices); the indices kept are
+    written next to it (`<name>_rows.npy` / `<name>_cols.npy`, float64).  Rank 0's engine; called once, after the timing."""
+    os.makedirs(path, exist_ok=True)
+    U, V = eng.get_factors(want_v=stack is None)
+    arrays = {"doc_topic": (U, 0), "log_likelihood_trace": (np.asarray(ll_trace, np.float32), None)}
+    if stack is None:
+        arrays["topic_word"] = (V, 1)
+    else:
+        arrays["topic_stack"] = (np.array(stack, np.float32).reshape(-1, stack.shape[-1]), 1)
+    for name, (a, axis) in arrays.items():
+        share = DUMP_SHARE_BYTES.get(name)
+        if share is not None and a.nbytes > share:
+            keep = share // (a.nbytes // a.shape[axis])
+            idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(a.shape[axis], size=keep, replace=False))
+            a = np.take(a, idx, axis=axis)
+            np.save(os.path.join(path, name + ("_rows" if axis == 0 else "_cols") + ".npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 CONFIG_SHORT = {(18_846, 20): "20NG-shaped 18846x173762, 2.95M nnz", (100_000, 32): "100k x 50k, 10M nnz",
                 (1_000_000, 64): "1M x 100k, 100M nnz", (5_000_000, 128): "5M x 200k, 500M nnz"}
 
@@ -600,23 +645,29 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS))
     ap.add_argument("--schedule", default=os.environ.get("PLSA_BENCH_SCHEDULE", "fused"),
                     choices=["fused", "materialised"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel regions, the materialised leg (roofline), the CPU baseline, the measured "
+                         "ensemble, the other BASELINE configs, the counter passes; the full object goes to --full-json")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed fit returned as DIR/<name>.npy (float32, at most 64 MB: "
+                         "a fixed, seeded sample of the rows / columns of the larger matrices)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="(default since round 5; kept for old command lines)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 counter passes")
-    ap.add_argument("--no-ensemble", action="store_true", help="skip the measured ensemble leg")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) skip the in-run rocprofv3 counter passes")
+    ap.add_argument("--no-ensemble", action="store_true", help="(--full) skip the measured ensemble leg")
     ap.add_argument("--members-per-rank", type=int, default=0,
                     help="members each rank fits in the measured ensemble leg (0 = 4, or 32 / N with --config 4)")
     ap.add_argument("--topics", type=int, default=-1,
                     help="generate a TOPICAL corpus of the config's shape (documents as Dirichlet mixtures of this many latent "
                          "topics; plsa_generate_synthetic_topics) instead of independent Zipf tokens; labelled in `config`.  "
                          "Default -1: 20 topics for the 20-Newsgroups configurations (1, 4), independent tokens (0) otherwise")
-    ap.add_argument("--full", action="store_true",
-                    help="print the FULL result object as the JSON line (tools); default: the compact line (the driver keeps a "
-                         "2000-character tail) and the full object in --full-json")
-    ap.add_argument("--full-json", default="", help="where the full result object goes (default gpurun_out/bench_full_cfgC_nN.json)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the compact legs of the other BASELINE configs")
+    ap.add_argument("--full-object", action="store_true",
+                    help="print the whole result object as the JSON line (tools); default: the compact line (the driver keeps a "
+                         "2000-character tail)")
+    ap.add_argument("--full-json", default="", help="(--full) where the full result object goes (default bench_out/bench_full_cfgC_nN.json)")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the compact legs of the other BASELINE configs")
     ap.add_argument("--cpu-baseline-sampled", action="store_true",
-                    help="time the CPU port on a bounded row sample (~15 s) instead of the whole corpus (config 3: ~45 s, 26 GB)")
+                    help="(--full) time the CPU port on a bounded row sample (~15 s) instead of the whole corpus (config 3: ~45 s, 26 GB)")
     ap.add_argument("--exchange", default="rccl", choices=["rccl", "files"],
                     help="files: TEST MODE for boxes with fewer GPUs than ranks (host-file exchange, shared GPUs)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -721,9 +772,69 @@ def main():
         assert it == args.warmup
     gather_components()
 
-    # ---- timed regions: three times exactly K EM iterations, each bracketed by barrier + synchronize; the
-    # MEDIAN region is reported (its per-kernel events, its wall time), all three are listed
+    # ---- the timed region: exactly K EM iterations from the initial factors, bracketed by barrier + synchronize, the
+    # engine's per-kernel HIP events off (two event records per launch cost ~1.5 % at config 3 and ~25 % at the 20NG shape,
+    # whose iteration is seven launches of 6-60 us)
     stage("timed")
+    eng.set_factors(U0, V0)
+    barrier()
+    t0 = time.perf_counter()
+    it, ll_trace = eng.fit(None, n_iter=args.steps, n_iter_per_test=10, tolerance=0.0, e_step_thresh=1e-32, flags=flags)
+    stack = gather_components()
+    barrier()
+    dt = float(comm.allreduce_f64([time.perf_counter() - t0], "max")[0])
+    assert it == args.steps, "early stop inside the timed region (%d of %d)" % (it, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, ll_trace, stack)
+
+    n_gpus = world
+    exchange = "none" if world == 1 else ("RCCL (C ABI, ncclAllGather)" if isinstance(comm, plsa_comm.RcclComm)
+                                          else "host files -- TEST MODE, ranks share %d GPU(s)" % n_dev)
+    out = {
+        "metric": "EM iterations/sec", "value": round(n_gpus * args.steps / dt, 4), "unit": "iter/s",
+        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "value_is": "one timed region of exactly %d iterations (barrier + synchronize around it, per-kernel events off, "
+                    "max over ranks)" % args.steps,
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": cfg["name"] + ("" if not corpus_options(args) else " -- TOPICAL corpus %r" % (corpus_options(args),)),
+                   "corpus": corpus_kind(corpus_options(args)),
+                   "n_docs": n, "n_vocab": m, "nnz": nnz, "k": k,
+                   "schedule": args.schedule,
+                   "parallelism": "single fit" if n_gpus == 1 else
+                   "ensemble: one bootstrap member per GPU x%d, all-gather of topics: %s" % (n_gpus, exchange),
+                   "ll_test_every": 10, "tolerance": 0.0, "e_step_thresh": 1e-32},
+        "rccl_ranks": world if isinstance(comm, plsa_comm.RcclComm) else 0,
+        "exchange": exchange,
+        "device": info["name"] or "AMD Instinct MI355X", "arch": info["arch"], "generate_s": round(t_gen, 2),
+    }
+    if args.full:
+        eng = full_legs(out, eng, comm, args, U0, V0, flags, barrier, gather_components, stage, rccl_init_s, device)
+    if world > 1:
+        comm.barrier()
+        plsa_comm.shutdown()
+    from enstop_amd.engine import reset_engines
+    reset_engines()
+    if rank == 0:
+        full_path = full_report(out, args) if args.full else None
+        line = out if args.full_object else compact_line(out, full_path)
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(line, separators=(",", ":")) + "\n").encode())
+    os.close(json_fd)
+
+
+def full_legs(out, eng, comm, args, U0, V0, flags, barrier, gather_components, stage, rccl_init_s, device):
+    """--full: everything beyond the headline -- per-kernel HIP-event regions, the materialised leg and its roofline, the CPU
+    port, the measured ensemble, every other BASELINE configuration.  Fills `out`; returns the engine in use at the end."""
+    from enstop_amd import comm as plsa_comm
+    from enstop_amd.engine import get_engine
+    world = n_gpus = out["n_gpus"]
+    rank = int(os.environ.get("RANK", "0"))
+    cfg = CONFIGS[args.config]
+    m, k = cfg["m"], cfg["k"]
+    n_act, _, nnz_act = eng.shape
+    # ---- three further regions of exactly K EM iterations with the per-kernel HIP events on, each bracketed by barrier +
+    # synchronize; the per-kernel figures come from the MEDIAN region, all three are listed
     regions = []
     stack = None
     for _region in range(3):
@@ -744,19 +855,8 @@ def main():
         dt_r = float(comm.allreduce_f64([dt_r], "max")[0])
         split = comm.allreduce_f64([t_fit, t_gather], "max")
         regions.append((dt_r, rep_r, float(split[0]), float(split[1])))
-    # one more region of the same K iterations WITHOUT the per-kernel HIP events (two event records per launch cost
-    # ~1.5 % at config 3 and ~25 % at the 20NG shape, whose iteration is seven launches of 6-60 us): reported next to
-    # `value`, never instead of it
-    eng.set_factors(U0, V0)
-    barrier()
-    t0 = time.perf_counter()
-    it, _ = eng.fit(None, n_iter=args.steps, n_iter_per_test=10, tolerance=0.0, e_step_thresh=1e-32, flags=flags)
-    gather_components()
-    barrier()
-    dt_plain = float(comm.allreduce_f64([time.perf_counter() - t0], "max")[0])
-    assert it == args.steps
     order = sorted(range(3), key=lambda i: regions[i][0])
-    dt, report, dt_fit, dt_gather = regions[order[1]]
+    _, report, dt_fit, dt_gather = regions[order[1]]
     schedule = eng.balance_info()            # measured XCD boundaries of the column pass (results do not depend on them)
     if stack is not None and rank == 0:
         assert stack.shape == (world, k, m) and np.all(np.isfinite(stack))
@@ -814,39 +914,17 @@ def main():
         mat = {"schedule": "materialised (reference kernel sequence)", "steps": it2, "p_placement": eng.placement_info(),
                "value": round(it2 / dt2, 4), "ms_per_step": round(dt2 / it2 * 1e3, 4), "kernels": kernels_mat}
 
-    n_gpus = world
-    exchange = "none" if world == 1 else ("RCCL (C ABI, ncclAllGather)" if isinstance(comm, plsa_comm.RcclComm)
-                                          else "host files -- TEST MODE, ranks share %d GPU(s)" % n_dev)
-    out = {
-        "metric": "EM iterations/sec", "value": round(n_gpus * args.steps / dt, 4), "unit": "iter/s",
-        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "value_is": "median of 3 back-to-back timed regions of exactly %d iterations (barrier + synchronize around each, "
-                    "max over ranks)" % args.steps,
-        "region_without_per_kernel_events": {"value": round(n_gpus * args.steps / dt_plain, 4),
-                                             "ms_per_step": round(dt_plain / args.steps * 1e3, 4),
-                                             "note": "a fourth region of the same K iterations with the engine's per-kernel "
-                                                     "HIP events off; `value` and the per-kernel figures come from the "
-                                                     "three regions that record them"},
+    out.update({
+        "value_is": out["value_is"] + "; the per-kernel figures come from the median of `timed_regions`",
         "timed_region_split_s": {"iterations": round(dt_fit, 5), "topic_gather_to_host": round(dt_gather, 5),
                                  "note": "max over ranks of the two parts of the median region; the gather (D2D into the stack, "
                                          "all-gather when N > 1, one copy to the host array) is INSIDE the timed region"},
         "timed_regions": [{"value": round(n_gpus * args.steps / r[0], 4), "ms_per_step": round(r[0] / args.steps * 1e3, 4)}
                           for r in regions],
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": cfg["name"] + ("" if not corpus_options(args) else " -- TOPICAL corpus %r" % (corpus_options(args),)),
-                   "corpus": corpus_kind(corpus_options(args)),
-                   "n_docs": n, "n_vocab": m, "nnz": nnz, "k": k,
-                   "schedule": args.schedule,
-                   "parallelism": "single fit" if n_gpus == 1 else
-                   "ensemble: one bootstrap member per GPU x%d, all-gather of topics: %s" % (n_gpus, exchange),
-                   "ll_test_every": 10, "tolerance": 0.0, "e_step_thresh": 1e-32},
-        "rccl_ranks": world if isinstance(comm, plsa_comm.RcclComm) else 0,
-        "exchange": exchange,
-        "gcell_per_s": round(nnz_total * k * args.steps / dt / 1e9, 3),
+        "gcell_per_s": round(nnz_total * k * out["value"] / n_gpus / 1e9, 3),
         # derived from the iteration rate alone (no bootstrap / structure build / init / gather): the MEASURED
         # figure is ensemble.fits_per_min below
-        "ensemble_fits_per_min_from_iteration_rate": round(n_gpus * args.steps / dt / FITS_ITERS * 60.0, 3),
+        "ensemble_fits_per_min_from_iteration_rate": round(out["value"] / FITS_ITERS * 60.0, 3),
         # north_star's roofline kernel: the per-nnz materialising E-step (HBM-bound)
         "roofline_note": "`roofline`: k_e_step, MATERIALISED schedule (second leg, `materialised_leg`; `value` never launches "
                          "it). `roofline_dominant_fused`: dominant kernel of the FUSED schedule that produces `value`, against "
@@ -858,8 +936,7 @@ def main():
         "kernels": kernels,
         "column_pass_schedule": schedule,
         "materialised_leg": mat,
-        "device": info["name"] or "AMD Instinct MI355X", "arch": info["arch"], "generate_s": round(t_gen, 2),
-    }
+    })
     if rank == 0:
         if n_gpus == 1 and not args.no_cpu_baseline:
             # the WHOLE corpus by default (config 3: 2 iterations, ~45 s of host time, 26 GB of host memory: nothing is
@@ -868,7 +945,7 @@ def main():
                 out["cpu_baseline"] = cpu_baseline(eng, cfg, k) if args.cpu_baseline_sampled else \
                     cpu_baseline(eng, cfg, k, iters=2, whole=True)
             except Exception as e:       # the baseline must never cost the GPU measurement
-                out["cpu_baseline"] = {"value": None, "unit": "iter/s", "cores": os.cpu_count(), "kind": "port",
+                out["cpu_baseline"] = {"value": None, "unit": "iter/s", "cores": host_threads(), "kind": "port",
                                        "sample": "failed: %r" % (e,)}
     # ---- measured ensemble: the product's own call, four members per rank (see the module docstring) -------------
     if not args.no_ensemble:
@@ -911,59 +988,57 @@ def main():
         _reset()                                   # config 5's materialised leg needs ~270 of the 288 GB
         eng = get_engine(device)
         leg("config5", lambda: quick_config(eng, 5, args.steps, args.warmup, args.seed, min_steps=20, device_init=True))
-    if world > 1:
-        comm.barrier()
-        plsa_comm.shutdown()
-    from enstop_amd.engine import reset_engines
-    reset_engines()
-    # ---- HBM-side traffic of the roofline kernels: PMC passes in this run, else the committed profile ----
-    if rank == 0:
-        table = None
-        if n_gpus == 1 and not args.no_pmc:
-            table = measure_traffic(args)
-        source = "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over " \
-                 "`bench.py --pmc-child`; (2 x FETCH_SIZE + WRITE_SIZE) KiB, FETCH_SIZE doubled per MI355X_MICROARCH.md"
-        if table is None:
-            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-            if os.path.exists(pmc):
-                try:
-                    table = json.load(open(pmc)).get("config%d" % args.config, {})
-                    source = "from_committed_profile"
-                except Exception:
-                    table = None
-        for key in ("roofline", "roofline_dominant_fused"):
-            rec = (table or {}).get(out[key]["kernel"])
-            if rec:
-                out[key]["traffic"] = rec["hbm_bytes_per_launch"]
-                out[key]["traffic_source"] = source if source != "from_committed_profile" else \
-                    "from_committed_profile: " + rec.get("source", "profiles/pmc_traffic.json")
-        # the driver-visible roofline object names BOTH kernels: the north-star one (k_e_step: not launched by the loop `value`
-        # times -- a separate, materialised leg) and, as `timed_loop`, the dominant kernel of the loop that IS timed
-        out["roofline"]["leg"] = "materialised (separate from value)" if mat is not None else "the timed loop itself (--schedule materialised)"
-        d_ = out["roofline_dominant_fused"]
-        tl = {"kernel": d_["kernel"], "avg_ms": d_["avg_launch_ms"], "algorithmic_GB": d_["algorithmic_GB_per_launch"],
-              "frac": d_["frac"], "traffic_GB": None, "traffic_ratio": None, "frac_on_traffic": None,
-              "share_of_ms_per_step": round(d_["avg_launch_ms"] / out["ms_per_step"], 3)}
-        if d_.get("traffic"):
-            tl["traffic_GB"] = round(d_["traffic"] / 1e9, 3)
-            tl["traffic_ratio"] = round(d_["traffic"] / 1e9 / d_["algorithmic_GB_per_launch"], 2)
-            tl["frac_on_traffic"] = round(d_["traffic"] / 1e9 / (d_["avg_launch_ms"] / 1e3) / HBM_PEAK_GBS, 4)
-        out["roofline"]["timed_loop"] = tl
-        if table and source != "from_committed_profile":
-            out["pmc_traffic"] = table
-        out["hot_kernels"] = hot_kernel_table(k, dict(kernels, **((mat or {}).get("kernels", {}))), table or {}, source)
-        sys.stdout.flush()
-        full_path = args.full_json or os.path.join(ROOT, "gpurun_out", "bench_full_cfg%d_n%d.json" % (args.config, n_gpus))
-        try:
-            os.makedirs(os.path.dirname(full_path) or ".", exist_ok=True)
-            with open(full_path, "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError as e:
-            print("bench.py: full result object not written (%r)" % (e,), file=sys.stderr)
-            full_path = None
-        line = out if args.full else compact_line(out, full_path and os.path.relpath(full_path, ROOT))
-        os.write(json_fd, (json.dumps(line, separators=(",", ":")) + "\n").encode())
-    os.close(json_fd)
+    return eng
+
+
+def full_report(out, args):
+    """--full, rank 0, after the engines are released: the HBM-side traffic of the roofline kernels (PMC passes in this run,
+    else the committed profile), `roofline.timed_loop`, `hot_kernels`; writes the full object to --full-json.  Returns that
+    path relative to the repository (None when it could not be written)."""
+    n_gpus, k, mat = out["n_gpus"], out["config"]["k"], out["materialised_leg"]
+    table = None
+    if n_gpus == 1 and not args.no_pmc:
+        table = measure_traffic(args)
+    source = "measured in this run: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over " \
+             "`bench.py --pmc-child`; (2 x FETCH_SIZE + WRITE_SIZE) KiB, FETCH_SIZE doubled per MI355X_MICROARCH.md"
+    if table is None:
+        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(pmc):
+            try:
+                table = json.load(open(pmc)).get("config%d" % args.config, {})
+                source = "from_committed_profile"
+            except Exception:
+                table = None
+    for key in ("roofline", "roofline_dominant_fused"):
+        rec = (table or {}).get(out[key]["kernel"])
+        if rec:
+            out[key]["traffic"] = rec["hbm_bytes_per_launch"]
+            out[key]["traffic_source"] = source if source != "from_committed_profile" else \
+                "from_committed_profile: " + rec.get("source", "profiles/pmc_traffic.json")
+    # the driver-visible roofline object names BOTH kernels: the north-star one (k_e_step: not launched by the loop `value`
+    # times -- a separate, materialised leg) and, as `timed_loop`, the dominant kernel of the loop that IS timed
+    out["roofline"]["leg"] = "materialised (separate from value)" if mat is not None else "the timed loop itself (--schedule materialised)"
+    d_ = out["roofline_dominant_fused"]
+    tl = {"kernel": d_["kernel"], "avg_ms": d_["avg_launch_ms"], "algorithmic_GB": d_["algorithmic_GB_per_launch"],
+          "frac": d_["frac"], "traffic_GB": None, "traffic_ratio": None, "frac_on_traffic": None,
+          "share_of_ms_per_step": round(d_["avg_launch_ms"] / out["ms_per_step"], 3)}
+    if d_.get("traffic"):
+        tl["traffic_GB"] = round(d_["traffic"] / 1e9, 3)
+        tl["traffic_ratio"] = round(d_["traffic"] / 1e9 / d_["algorithmic_GB_per_launch"], 2)
+        tl["frac_on_traffic"] = round(d_["traffic"] / 1e9 / (d_["avg_launch_ms"] / 1e3) / HBM_PEAK_GBS, 4)
+    out["roofline"]["timed_loop"] = tl
+    if table and source != "from_committed_profile":
+        out["pmc_traffic"] = table
+    out["hot_kernels"] = hot_kernel_table(k, dict(out["kernels"], **((mat or {}).get("kernels", {}))), table or {}, source)
+    full_path = args.full_json or os.path.join(ROOT, "bench_out", "bench_full_cfg%d_n%d.json" % (args.config, n_gpus))
+    try:
+        os.makedirs(os.path.dirname(full_path) or ".", exist_ok=True)
+        with open(full_path, "w") as f:
+            json.dump(out, f, indent=1)
+    except OSError as e:
+        print("bench.py: full result object not written (%r)" % (e,), file=sys.stderr)
+        return None
+    return os.path.relpath(full_path, ROOT)
 
 
 if __name__ == "__main__":

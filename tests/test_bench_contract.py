@@ -97,3 +97,53 @@ def test_the_printed_line_is_compact_and_carries_the_timed_loop_roofline():
     assert b.corpus_options(types.SimpleNamespace(topics=-1, config=4))["topics"] == 20
     assert b.corpus_options(types.SimpleNamespace(topics=-1, config=3)) == {}
     assert b.corpus_options(types.SimpleNamespace(topics=0, config=1)) == {}
+
+
+def test_dump_outputs_are_float32_bounded_and_seeded(tmp_path):
+    """--dump-outputs: the timed fit's factors and likelihood trace as float32 .npy files, at most 64 MB in all; a matrix above
+    its share keeps a fixed, seeded sample of its rows / columns (indices written next to it), the same in every run."""
+    import numpy as np
+    b = _bench()
+    rs = np.random.RandomState(0)
+    n, m, k = 200_000, 150_000, 64                            # P(z|d) 51 MB, P(w|z) 38 MB: both above their shares
+    U, V = rs.rand(n, k).astype(np.float32), rs.rand(k, m).astype(np.float32)
+
+    class Eng:
+        def get_factors(self, want_u=True, want_v=True):
+            return (U if want_u else None), (V if want_v else None)
+    trace = np.array([-9.5, -9.25], np.float32)
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), Eng(), trace, None)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) == ["doc_topic.npy", "doc_topic_rows.npy", "log_likelihood_trace.npy",
+                                                           "topic_word.npy", "topic_word_cols.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        a, a2 = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, a2), f
+    load = lambda f: np.load(tmp_path / "a" / (f + ".npy"))
+    rows, cols = load("doc_topic_rows").astype(np.int64), load("topic_word_cols").astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.all(np.diff(cols) > 0)
+    assert np.array_equal(load("doc_topic"), U[rows]) and np.array_equal(load("topic_word"), V[:, cols])
+    assert np.array_equal(load("log_likelihood_trace"), trace)
+    # N > 1: the gathered stack of every rank's topics takes the topic matrix's place
+    stack = rs.rand(2, k, 1000).astype(np.float32)
+    b.dump_outputs(str(tmp_path / "c"), Eng(), trace, stack)
+    assert np.array_equal(np.load(tmp_path / "c" / "topic_stack.npy"), stack.reshape(2 * k, 1000))
+    assert not os.path.exists(tmp_path / "c" / "topic_word.npy")
+
+
+def test_the_plain_line_carries_the_contract_keys():
+    """A plain run (no --full) measures only the headline: its line holds the contract keys and the config, nothing that
+    needs a leg of its own."""
+    b = _bench()
+    out = {"metric": "EM iterations/sec", "value": 310.5, "unit": "iter/s", "n_gpus": 1, "steps": 20, "warmup": 5,
+           "ms_per_step": 3.2206, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+           "data": "synthetic", "config": {"n_docs": 1_000_000, "k": 64, "nnz": 100_435_863, "schedule": "fused",
+                                           "corpus": b.corpus_kind({}), "parallelism": "single fit"},
+           "rccl_ranks": 0, "exchange": "none"}
+    line = b.compact_line(out)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert line[key] == out[key], key
+    assert line["config"]["k"] == 64 and line["config"]["schedule"] == "fused"
+    assert not {"roofline", "cpu_baseline", "timed_regions", "other_configs", "ensemble", "full"} & set(line)

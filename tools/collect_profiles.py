@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the scratch output of tools/gpu_profile.sh (gpurun_out/) into the committed evidence under
+"""Turn the scratch output of tools/gpu_profile.sh (bench_out/) into the committed evidence under
 profiles/: bench lines per config, the rocprofv3 --kernel-trace --stats table of the default bench
 command (csv + a readable summary), the FETCH_SIZE / WRITE_SIZE PMC passes and the per-kernel HBM
 traffic file bench.py reads (profiles/pmc_traffic.json).   usage: python tools/collect_profiles.py r01"""
@@ -11,7 +11,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, "bench_out")
 P = os.path.join(ROOT, "profiles")
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 
@@ -86,7 +86,8 @@ if os.path.exists(f):
     shutil.copy(f, os.path.join(P, "%s_rocprofv3_kernel_stats_bench_cfg3.csv" % tag))
     rows = list(csv.DictReader(open(f)))
     with open(os.path.join(P, "%s_rocprofv3_kernel_stats_bench_cfg3.summary.txt" % tag), "w") as o:
-        o.write("rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline   (config 3, 1x MI355X)\n")
+        o.write("rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --full-object --no-cpu-baseline "
+                "--no-pmc --no-ensemble --no-other-configs   (config 3, 1x MI355X)\n")
         o.write("HIP-event figures of the SAME process: profiles/%s_bench_cfg3_under_rocprofv3.json\n" % tag)
         o.write("%-62s %6s %12s %12s %12s %8s\n" % ("kernel", "calls", "avg_ms", "min_ms", "max_ms", "pct"))
         for r in rows[:40]:

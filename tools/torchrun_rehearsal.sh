@@ -12,5 +12,5 @@ echo "== N=2 under torchrun, --exchange files (labelled test mode)"
 $L --nproc-per-node 2 --master-port 29513 bench.py --gpus 2 $B --exchange files 2>/tmp/e3 | cut -c1-260; echo "rc ${PIPESTATUS[0]}"
 grep -E "enstop_amd rank" /tmp/e3 | head -3
 echo "== N=2 under torchrun, files, rank 1 dies in the ensemble leg (survivor must report its stage when torchrun tears the job down)"
-PLSA_BENCH_FAIL_AT=1:ensemble $L --nproc-per-node 2 --master-port 29514 bench.py --gpus 2 $B --exchange files > /tmp/o4 2>/tmp/e4; echo "rc $? stdout bytes $(wc -c < /tmp/o4)"
+PLSA_BENCH_FAIL_AT=1:ensemble $L --nproc-per-node 2 --master-port 29514 bench.py --gpus 2 $B --full --exchange files > /tmp/o4 2>/tmp/e4; echo "rc $? stdout bytes $(wc -c < /tmp/o4)"
 grep -E "enstop_amd rank|exits at stage" /tmp/e4 | cut -c1-400 | head -6
