@@ -93,6 +93,11 @@ struct plsa_ctx {
     i64 n_items = 0;
     DevBuf colptr, csc_row, csc_val, csc_pos, item_first, item_col, item_start, item_order, partial, heavy_cols;
     bool use_item_order = true, xcd_split = true;
+    // packed entry streams of the fused passes (plsa_kernels.hpp: Packed): pk_csr parallel to col / val, pk_csc parallel to
+    // csc_row / csc_val.  A stream is used (pk_*_ok) when its ids fit 24 bits and at most 1/16 of the entries escape.
+    bool packed = true;              // PLSA_PACKED=0: the two-array streams everywhere (A/B)
+    bool pk_csr_valid = false, pk_csr_ok = false, pk_csc_valid = false, pk_csc_ok = false;
+    DevBuf pk_csr, pk_csc, pk_count;
     int chunks_per_lane = 2;
     int row_lpn = 1, row_ch = 1;     // lane shape of the DOCUMENT pass (may differ from lpn / ch: see set_shape)
     bool row_shape_8x2 = true;       // PLSA_ROW_SHAPE=0: document pass in the common shape
@@ -557,6 +562,8 @@ void set_active_pointers(plsa_ctx *c) {
     }
     c->rowidx_valid = false;
     c->csc_valid = false;
+    c->pk_csr_valid = false;
+    c->pk_csc_valid = false;
     c->roworder_valid = false;
     c->ritems_valid = false;
     c->eitems_valid = false;
@@ -724,6 +731,15 @@ int ensure_csc(plsa_ctx *c) {
     CHK(ensure(c, c->csc_pos, sizeof(int) * (size_t)nnz));
     CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)std::max<i64>(nnz, m + 1)));  // counts, then sorted keys
     CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)nnz));                         // iota
+    // the column pass' packed stream is written by the same gather (documents are its ids)
+    const bool pack = c->packed && nnz > 0 && c->n <= plsa::PACK_MAX_IDS;
+    c->pk_csc_valid = false;
+    c->pk_csc_ok = false;
+    if (pack) {
+        CHK(ensure(c, c->pk_csc, sizeof(unsigned) * (size_t)nnz));
+        CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
+    }
     // stable sort of entry positions by column: within a column entries stay in document order
     if (nnz > 0) {
         hipLaunchKernelGGL(plsa::k_iota, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
@@ -742,7 +758,8 @@ int ensure_csc(plsa_ctx *c) {
                            c->tmp0.as<int>(), nnz, (int)m, c->colptr.as<int>());
         hipLaunchKernelGGL(plsa::k_csc_gather, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
                            c->csc_pos.as<int>(), c->rowidx.as<int>(), c->val, nnz,
-                           c->csc_row.as<int>(), c->csc_val.as<float>());
+                           c->csc_row.as<int>(), c->csc_val.as<float>(), pack ? c->pk_csc.as<unsigned>() : nullptr,
+                           pack ? c->pk_count.as<unsigned long long>() : nullptr);
         CHK(launch_check(c, "k_csc_gather"));
     } else {
         HIPCHK(c, hipMemsetAsync(c->colptr.p, 0, sizeof(int) * (size_t)(m + 1), c->stream));
@@ -809,8 +826,51 @@ int ensure_csc(plsa_ctx *c) {
                        c->heavy_cols.as<int>() + m);
     CHK(launch_check(c, "k_heavy_list"));
     HIPCHK(c, hipMemcpyAsync(&c->n_heavy, c->heavy_cols.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    unsigned long long escaped = 0;
+    if (pack) HIPCHK(c, hipMemcpyAsync(&escaped, c->pk_count.p, sizeof escaped, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->csc_valid = true;
+    c->pk_csc_valid = c->packed;
+    c->pk_csc_ok = pack && escaped * 16 <= (unsigned long long)nnz;
+    if (!c->pk_csc_ok) release(c->pk_csc);
+    return 0;
+}
+
+// Packed entry stream of one pass (plsa_kernels.hpp: Packed) from its (id, count) arrays; *ok: the stream is eligible
+// (ids below 2^24 -- `id_range` of them -- and at most 1/16 of the entries escaped to the float array).  An ineligible
+// stream is not kept: its pass runs on the two arrays.
+int build_packed(plsa_ctx *c, DevBuf &out, const int *ids, const float *vals, i64 id_range, bool *ok) {
+    *ok = false;
+    const i64 nnz = c->nnz;
+    if (nnz <= 0 || id_range > plsa::PACK_MAX_IDS) { release(out); return 0; }
+    CHK(ensure(c, out, sizeof(unsigned) * (size_t)nnz));
+    CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(plsa::k_pack_entries, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
+                       ids, vals, nnz, out.as<unsigned>(), c->pk_count.as<unsigned long long>());
+    CHK(launch_check(c, "k_pack_entries"));
+    unsigned long long escaped = 0;
+    HIPCHK(c, hipMemcpyAsync(&escaped, c->pk_count.p, sizeof escaped, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *ok = escaped * 16 <= (unsigned long long)nnz;
+    if (!*ok) release(out);
+    return 0;
+}
+
+// the document pass' packed stream: built on the first fused pass after an upload / bootstrap / generate
+int ensure_packed_csr(plsa_ctx *c) {
+    if (!c->packed || c->pk_csr_valid) return 0;
+    CHK(build_packed(c, c->pk_csr, c->col, c->val, c->m, &c->pk_csr_ok));
+    c->pk_csr_valid = true;
+    return 0;
+}
+
+// the column pass' packed stream: written by ensure_csc; rebuilt from the CSC arrays after plsa_release_scratch
+int ensure_packed_csc(plsa_ctx *c) {
+    CHK(ensure_csc(c));
+    if (!c->packed || c->pk_csc_valid) return 0;
+    CHK(build_packed(c, c->pk_csc, c->csc_row.as<int>(), c->csc_val.as<float>(), c->n, &c->pk_csc_ok));
+    c->pk_csc_valid = true;
     return 0;
 }
 
@@ -975,19 +1035,27 @@ int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, floa
     const int rseg = c->rseg;
     const i64 n_ritems = c->n_ritems;
     if (want_ll) CHK(ensure(c, c->ll_partials, sizeof(double) * (size_t)grid));
+    if (!from_p) CHK(ensure_packed_csr(c));
+    const bool packed = !from_p && c->packed && c->pk_csr_ok;
     CHK(dispatch_shape_row(c, [&](auto S) {
         using Sh = decltype(S);
-        const int *ip = c->indptr, *cl = c->col;
+        const int *ip = c->indptr, *cl = packed ? c->pk_csr.as<int>() : c->col;
         const float *vl = c->val, *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
         const float *P = p_base(c);
         float *Un = c->U[out_u(c)].as<float>();
         double *llp = c->ll_partials.as<double>();
         const int n = (int)c->n, kp = c->kp;
-        auto go = [&](auto FP, auto LL, auto TN, const char *name) {
+        auto launch = [&](auto SS, auto FP, auto LL, auto TN, const char *name) {
             Scope s(c, name);
-            hipLaunchKernelGGL((plsa::k_row_pass<Sh, decltype(FP)::value, decltype(LL)::value, decltype(TN)::value>),
+            hipLaunchKernelGGL((plsa::k_row_pass<decltype(SS), decltype(FP)::value, decltype(LL)::value, decltype(TN)::value>),
                                dim3(grid), dim3(256), 0, c->ls, ip, cl, vl, n, order, U, Vt, P, Un,
                                d_sw, d_norm_pdz, kp, thresh, llp, ri_row, ri_start, rseg, n_ritems, rpart, xcd_rows ? 1 : 0);
+        };
+        auto go = [&](auto FP, auto LL, auto TN, const char *name) {   // fused: the packed entry stream when it is eligible
+            if constexpr (!decltype(FP)::value) {
+                if (packed) { launch(plsa::Packed<Sh>{}, FP, LL, TN, name); return; }
+            }
+            launch(Sh{}, FP, LL, TN, name);
         };
         using T = std::true_type;
         using F = std::false_type;
@@ -1113,7 +1181,8 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
 // parts: 1 = the column pass itself, 2 = the un-normalised per-column sums of its partials (k_col_reduce),
 //        3 = both
 int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int parts = 3) {
-    CHK(ensure_csc(c));
+    CHK(from_p ? ensure_csc(c) : ensure_packed_csc(c));
+    const bool packed = !from_p && c->packed && c->pk_csc_ok;
     CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->n_items, 1) * c->kp));
     int rc = 0;
     CHK(dispatch_shape_gather(c, table_is_wide(c, c->n), [&](auto S) {     // the pass gathers P(z|d) rows: n of them
@@ -1137,16 +1206,23 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
                     grid = std::min(grid, c->small_grid * c->prop.multiProcessorCount);
                 Scope s(c, from_p ? "k_col_pass<P>" : "k_col_pass<fused>");
                 const int4 *rec = c->item_rec.as<int4>();
-                const int *lo = c->xcd_lo.as<int>(), *cr = c->csc_row.as<int>(), *cp = c->csc_pos.as<int>();
+                const int *lo = c->xcd_lo.as<int>(), *cp = c->csc_pos.as<int>();
+                const int *cr = packed ? c->pk_csc.as<int>() : c->csc_row.as<int>();
                 const float *cvl = c->csc_val.as<float>(), *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
                 float *part = c->partial.as<float>();
                 double *sums = c->colsum_rows.as<double>();
                 unsigned long long *te = c->t_end.as<unsigned long long>();
                 const int kp = c->kp;
-                auto go = [&](auto FP, auto TM, auto TN) {
-                    hipLaunchKernelGGL((plsa::k_col_pass<Sh, decltype(FP)::value, decltype(TM)::value, decltype(TN)::value>),
+                auto run = [&](auto SS, auto FP, auto TM, auto TN) {
+                    hipLaunchKernelGGL((plsa::k_col_pass<decltype(SS), decltype(FP)::value, decltype(TM)::value, decltype(TN)::value>),
                                        dim3(grid), dim3(256), smem, c->ls, rec, n_visit, lo, cr, cvl, cp, U, Vt, p_base(c), d_sw,
                                        part, kp, thresh, xcd_split, sums, te);
+                };
+                auto go = [&](auto FP, auto TM, auto TN) {   // fused: the packed entry stream when it is eligible
+                    if constexpr (!decltype(FP)::value) {
+                        if (packed) { run(plsa::Packed<Sh>{}, FP, TM, TN); return; }
+                    }
+                    run(Sh{}, FP, TM, TN);
                 };
                 using T = std::true_type;
                 using F = std::false_type;
@@ -1720,6 +1796,7 @@ int plsa_create(int device, plsa_ctx **out) {
     if (const char *s = getenv("PLSA_OVERLAP")) c->overlap = atoi(s) != 0;
     if (const char *s = getenv("PLSA_OVERLAP_FULL_LIMIT")) c->overlap_full_limit = atof(s);
     if (const char *s = getenv("PLSA_ROW_ITEMS")) c->ritems_mode = atoi(s);
+    if (const char *s = getenv("PLSA_PACKED")) c->packed = atoi(s) != 0;
     if (const char *s = getenv("PLSA_ROW_SEG")) c->rseg_override = std::max(1, atoi(s));
     int mult = 128;  // blocks per CU a grid may hold: large (but bounded) grids measured best
     if (const char *s = getenv("PLSA_GRID_MULT")) mult = std::max(1, atoi(s));
@@ -2313,7 +2390,8 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                 // the document pass (VALU-heavy, gathers the small topic table) and the column chain
                 // (fabric-bound gathers of P(z|d) rows) read the same current factors and write
                 // disjoint outputs: run them on two streams so their stalls overlap
-                CHK(ensure_csc(c));
+                CHK(ensure_packed_csc(c));
+                CHK(ensure_packed_csr(c));
                 CHK(ensure_ritems(c));
                 const int *unused = nullptr;
                 if (!c->use_ritems) CHK(ensure_roworder(c, &unused));
@@ -2854,6 +2932,12 @@ int plsa_schedule_info(plsa_ctx *c, int32_t *xcd_lo, double *xcd_end_us, int32_t
     return 0;
 }
 
+int plsa_packed_info(plsa_ctx *c, int32_t *csr, int32_t *csc) {
+    if (csr) *csr = !c->packed ? 0 : (c->pk_csr_valid ? (c->pk_csr_ok ? 1 : 0) : -1);
+    if (csc) *csc = !c->packed ? 0 : (c->csc_valid && c->pk_csc_valid ? (c->pk_csc_ok ? 1 : 0) : -1);
+    return 0;
+}
+
 int plsa_release_scratch(plsa_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2863,6 +2947,10 @@ int plsa_release_scratch(plsa_ctx *c) {
     c->p_lent = false;
     release(c->ref_terms); release(c->ref_csum); release(c->ref_pairs); release(c->ref_exps); release(c->ref_ll_neg); release(c->ref_heavy); release(c->ref_pairs2); release(c->ref_exps2); release(c->ref_tsum);
     release(c->partial); release(c->tmp0); release(c->tmp1); release(c->tmp2); release(c->cubtmp);
+    // packed entry streams (rebuilt by the next fused pass; the CSC arrays they are packed from stay)
+    release(c->pk_csr); release(c->pk_csc); release(c->pk_count);
+    c->pk_csr_valid = c->pk_csc_valid = false;
+    c->pk_csr_ok = c->pk_csc_ok = false;
     release(c->mt_words); release(c->mt_state); release(c->mt_fin); release(c->mt_poly); release(c->mt_seq);
     // member stack + gather buffers of the ensemble exchange (16 runs x 64 topics x 100 k words = 0.4 GB): re-created
     // by the next plsa_stack_reserve / plsa_comm_allgather_stack

@@ -109,7 +109,31 @@ struct Shape {
     // offset of chunk j for lane li, and whether it lies inside the row
     __device__ static __forceinline__ int c4(int li, int j) { return 4 * (li + LPN_ * j); }
     __device__ static __forceinline__ bool ok(int li, int j, int kp) { return FULL_ || c4(li, j) < kp; }
+    static constexpr bool PACKED = false;
 };
+
+// Packed entry stream of the fused passes (k_row_pass / k_col_pass with FROM_P = false): one 32-bit word per non-zero,
+// e = id | code << 24, position-parallel to the (id, count) arrays it was packed from.  code = the count when that is an
+// integer in 1..255, else 0: an ESCAPE, the count is then read from the float array at the same position.  (float)code is
+// exactly the count, so both forms feed the same x to the same arithmetic; the index stream shrinks from 8 to 4 bytes per
+// entry.  The flag rides on the shape type (Packed<S>) rather than behind it: the kernels' own template flags, which
+// the profiling tools read from the kernel names, stay as they are.
+template <class S>
+struct Packed : S {
+    static constexpr bool PACKED = true;
+};
+constexpr long long PACK_MAX_IDS = 1ll << 24;   // ids below 2^24 fit the word
+__device__ __forceinline__ unsigned pack_code(float v) {
+    return (v >= 1.f && v <= 255.f && v == truncf(v)) ? (unsigned)v : 0u;   // NaN, zeros, fractions, > 255: escape
+}
+// word -> (id, count) in the lane that loaded it; j: the entry's position, j_end: the end of the stream piece (lanes past
+// it hold the word 0 and keep the count 0).  The escape load is exec-masked: a wave without an escaped lane skips it.
+__device__ __forceinline__ void unpack_entry(int &id, float &x, const float *__restrict__ vals, int j, int j_end) {
+    const unsigned e = (unsigned)id;
+    id = (int)(e & 0xFFFFFFu);
+    x = (float)(e >> 24);                          // v_cvt_f32_ubyte3
+    if (x == 0.f && j < j_end) x = ldf(vals + j);
+}
 
 // gather the lane's chunks of one factor row WITHOUT a branch: out-of-row chunks read offset 0
 // (a valid address) -- ZERO_INVALID then forces them to zero (needed for one operand only:
@@ -330,6 +354,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_e_step_rows(const int *__re
 // A group owns one row: no atomics on U, the row norm is a group sum, the normalised row is written
 // once.  Rows are visited through `row_order` (descending length) so the groups of a wave finish
 // together; entries beyond the row end are padded with (word 0, count 0) and add exact zeros.
+// S = Packed<...> (fused only): `colidx` is the packed entry stream, `vals` is read for escaped entries only.
 // ------------------------------------------------------------------------------------------------
 template <class S, bool FROM_P, bool WANT_LL, bool TINY = false>
 __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restrict__ indptr,
@@ -372,15 +397,17 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restr
         for (int j = 0; j < CH; ++j) acc[j] = zero4();
         const float swd = (WANT_LL && sw) ? sw[d] : 1.0f;
         // software-pipelined index stream: the next LPN (word, count) pairs are in flight while the
-        // current ones are consumed
+        // current ones are consumed (S::PACKED: one packed word per entry, colidx holds the packed stream)
         int w_n = (j0 + li < j1) ? ldi(colidx + j0 + li) : 0;
-        float x_n = (j0 + li < j1) ? ldf(vals + j0 + li) : 0.f;
+        float x_n = (!S::PACKED && j0 + li < j1) ? ldf(vals + j0 + li) : 0.f;
         for (int jb = j0; jb < j1; jb += LPN) {
-            const int w_l = w_n;
-            const float x_l = x_n;
+            int w_l = w_n;
+            float x_l = x_n;
+            // unpacked BEFORE the next words are requested: an escape load then waits for itself only
+            if (S::PACKED) unpack_entry(w_l, x_l, vals, jb + li, j1);
             const int jn = jb + LPN + li;
             w_n = jn < j1 ? ldi(colidx + jn) : 0;
-            x_n = jn < j1 ? ldf(vals + jn) : 0.f;
+            if (!S::PACKED) x_n = jn < j1 ? ldf(vals + jn) : 0.f;
             const int cnt = min(LPN, j1 - jb);
             for (int s0 = 0; s0 < cnt; s0 += UNR) {
                 float4 a[UNR][CH];   // Vt rows (fused) or P rows (FROM_P)
@@ -546,7 +573,8 @@ __global__ void k_ritem_fill(const int *__restrict__ indptr, const int *__restri
 // partial k-vector; k_col_reduce* add the partials of a column in item order (bit-reproducible).
 // Items are visited through `item_order` (ascending first document) so that the groups running
 // concurrently gather from the same band of U rows.  FROM_P = false recomputes the
-// responsibilities from U (gather) and Vt (registers).
+// responsibilities from U (gather) and Vt (registers).  S = Packed<...> (fused only): `csc_row` is the packed
+// entry stream of the CSC order, `csc_val` is read for escaped entries only.
 // ------------------------------------------------------------------------------------------------
 // block-wide sum of per-thread k-vector chunks (float) in float64, fixed group order -> out_row[kp]
 template <class S, int THREADS = 256>
@@ -676,14 +704,16 @@ __global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__
             float4 vt[CH];
             load_row<S, true, PLSA_NT_STREAMS>(Vt + (i64)w * kp, li, kp, vt);
             int d_n = (j0 + li < j1) ? ldi(csc_row + j0 + li) : 0;
-            float x_n = (j0 + li < j1) ? ldf(csc_val + j0 + li) : 0.f;
+            float x_n = (!S::PACKED && j0 + li < j1) ? ldf(csc_val + j0 + li) : 0.f;
             int p_n = (FROM_P && j0 + li < j1) ? ldi(csc_pos + j0 + li) : 0;
             for (int jb = j0; jb < j1; jb += LPN) {
-                const int d_l = d_n, p_l = p_n;
+                int d_l = d_n;
+                const int p_l = p_n;
                 float x_l = x_n;
+                if (S::PACKED) unpack_entry(d_l, x_l, csc_val, jb + li, j1);   // (see k_row_pass)
                 const int jn = jb + LPN + li;
                 d_n = jn < j1 ? ldi(csc_row + jn) : 0;
-                x_n = jn < j1 ? ldf(csc_val + jn) : 0.f;
+                if (!S::PACKED) x_n = jn < j1 ? ldf(csc_val + jn) : 0.f;
                 if (FROM_P) p_n = jn < j1 ? ldi(csc_pos + jn) : 0;
                 if (sw) x_l *= sw[d_l];  // t = s * sample_weight[d]  (plsa.py:294), folded into the count
                 const int cnt = min(LPN, j1 - jb);
@@ -1198,14 +1228,41 @@ __global__ void k_init_rows(float *__restrict__ A, i64 rows, int k, int kp, unsi
         for (int z = lane; z < k; z += 64) A[r * kp + z] /= part;
     }
 }
-__global__ void k_csc_gather(const int *__restrict__ pos, const int *__restrict__ rowidx,
-                             const float *__restrict__ vals, i64 nnz, int *__restrict__ csc_row,
-                             float *__restrict__ csc_val) {
+// adds the escaped entries counted by each thread into *n_esc: one integer atomic per wave (all 64 lanes present)
+__device__ __forceinline__ void add_escapes(unsigned esc, unsigned long long *__restrict__ n_esc) {
+    for (int o = 32; o > 0; o >>= 1) esc += __shfl_xor(esc, o, 64);
+    if ((threadIdx.x & 63) == 0 && esc) atomicAdd(n_esc, (unsigned long long)esc);
+}
+// packed entry words of a stream (see Packed): packed[i] = ids[i] | pack_code(vals[i]) << 24, escapes counted into *n_esc
+__global__ __launch_bounds__(256) void k_pack_entries(const int *__restrict__ ids, const float *__restrict__ vals, i64 nnz,
+                                                      unsigned *__restrict__ packed, unsigned long long *__restrict__ n_esc) {
+    unsigned esc = 0;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (i64)gridDim.x * blockDim.x) {
+        const unsigned code = pack_code(vals[i]);
+        packed[i] = (unsigned)ids[i] | (code << 24);
+        esc += code == 0u;
+    }
+    add_escapes(esc, n_esc);
+}
+// CSC arrays in column order; `packed` (optional): the column pass' packed entry stream, escapes counted into *n_esc
+__global__ __launch_bounds__(256) void k_csc_gather(const int *__restrict__ pos, const int *__restrict__ rowidx,
+                                                    const float *__restrict__ vals, i64 nnz, int *__restrict__ csc_row,
+                                                    float *__restrict__ csc_val, unsigned *__restrict__ packed,
+                                                    unsigned long long *__restrict__ n_esc) {
+    unsigned esc = 0;
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (i64)gridDim.x * blockDim.x) {
         const int p = pos[i];
-        csc_row[i] = rowidx[p];
-        csc_val[i] = vals[p];
+        const int r = rowidx[p];
+        const float v = vals[p];
+        csc_row[i] = r;
+        csc_val[i] = v;
+        if (packed) {
+            const unsigned code = pack_code(v);
+            packed[i] = (unsigned)r | (code << 24);
+            esc += code == 0u;
+        }
     }
+    if (packed) add_escapes(esc, n_esc);
 }
 __global__ void k_item_counts(const int *__restrict__ colptr, int m, int seg, int *__restrict__ cnt) {
     const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;

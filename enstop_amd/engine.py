@@ -458,6 +458,13 @@ class Engine:
         return dict(xcd_chunk_boundaries=list(lo), xcd_finish_us=[round(v, 1) for v in t], timed_launches=n.value,
                     item_entries=seg.value, n_items=items.value)
 
+    def packed_info(self):
+        """Index stream of each fused pass for the current structure: 'packed', 'arrays' or None (not built yet)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        self._ok(self._L.plsa_packed_info(self._h, C.byref(a), C.byref(b)))
+        name = {1: "packed", 0: "arrays", -1: None}
+        return dict(csr=name[a.value], csc=name[b.value])
+
     def release_scratch(self):
         """Free the materialised P and other large scratch buffers (re-created on demand)."""
         self._ok(self._L.plsa_release_scratch(self._h))

@@ -76,6 +76,11 @@ int plsa_placement_info(plsa_ctx *ctx, int32_t *candidates, double *best_gbps, d
 int plsa_schedule_info(plsa_ctx *ctx, int32_t *xcd_lo /*[9]*/, double *xcd_end_us /*[8]*/, int32_t *timed_launches,
                        int32_t *item_len, int64_t *n_items);
 
+/* Index streams of the fused passes for the current structure: 1 = the packed entry stream (one 32-bit word per non-zero,
+ * id | count << 24 with an escape to the float array), 0 = the (index, value) arrays (ineligible
+ * stream, or PLSA_PACKED=0), -1 = not built yet.  csr: the document pass, csc: the column pass.  Any pointer may be NULL. */
+int plsa_packed_info(plsa_ctx *ctx, int32_t *csr, int32_t *csc);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * HIP events on the context's own stream around every kernel launch (bench.py roofline figures).  */
 int plsa_timing_enable(plsa_ctx *ctx, int32_t on);
