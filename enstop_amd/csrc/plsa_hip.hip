@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -51,26 +52,71 @@ thread_local std::string g_err;  // errors before a context exists
 // setenv("GPU_MAX_HW_QUEUES", "8", 0) itself before its first HIP call.  plsa_hw_queues() reports what
 // this process runs with.
 
+// Device memory, freed with its holder.  A BORROWED buffer (plsa_p_borrow) only views memory lent by someone else: it is
+// never freed here, and release() leaves it in place (borrow(nullptr) ends the loan).
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    bool borrowed = false;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { DevBuf(std::move(o)).swap(*this); return *this; }   // (the old memory goes with the temporary)
+    void swap(DevBuf &o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(borrowed, o.borrowed); }
+    ~DevBuf() { if (p && !borrowed) (void)hipFree(p); }
+    void release() { if (!borrowed) *this = DevBuf(); }
+    void borrow(void *q, size_t bytes) { *this = DevBuf(); p = q; cap = q ? bytes : 0; borrowed = q != nullptr; }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// owning HIP stream / event handle; converts to the raw handle wherever one is passed
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle &&o) noexcept { std::swap(h, o.h); }
+    Handle &operator=(Handle &&o) noexcept { Handle(std::move(o)).swap(*this); return *this; }
+    void swap(Handle &o) noexcept { std::swap(h, o.h); }
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+
+// page-locked host memory
+struct HostFree { void operator()(void *p) const { (void)hipHostFree(p); } };
+template <class T> using Pinned = std::unique_ptr<T[], HostFree>;
+template <class T> hipError_t host_alloc(Pinned<T> &h, size_t count) {
+    h.reset();
+    void *q = nullptr;
+    const hipError_t e = hipHostMalloc(&q, sizeof(T) * count, hipHostMallocDefault);
+    h.reset(static_cast<T *>(q));
+    return e;
+}
+
+// A structure derived from the active matrix, the lane shape or P(z|w,d).  Only its builder (ensure_*) marks it valid;
+// invalidate() keeps its allocations for the next build (bootstrap members reuse them), drop() frees them as well.
+template <class T> struct Derived {
+    bool valid = false;
+    void invalidate() { valid = false; }
+    void drop() { static_cast<T &>(*this) = T{}; }
 };
 
 struct Timed {
     int name_id;
-    hipEvent_t a, b;
+    Event a, b;
 };
 
 }  // namespace
 
+// Every resource is owned by its member and freed with the context; the streams come first, so that they outlive the
+// buffers and events declared after them.
 struct plsa_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // column-side chain of the fused iteration (overlaps the document pass)
-    hipStream_t ls = nullptr;        // stream the kernel wrappers currently launch on
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_row = nullptr, ev_tail = nullptr;   // pipelined small-corpus iteration: document pass done / column chain done
+    Stream stream;
+    Stream stream2;                  // column-side chain of the fused iteration (overlaps the document pass)
+    hipStream_t ls = nullptr;        // stream the kernel wrappers currently launch on (LaunchOn)
+    Event ev_fork, ev_join;
+    Event ev_row, ev_tail;           // pipelined small-corpus iteration: document pass done / column chain done
     bool overlap = true;
     double overlap_full_limit = 2e9;   // nnz * kp below which both passes run side by side (PLSA_OVERLAP_FULL_LIMIT)
     std::string err;
@@ -82,63 +128,73 @@ struct plsa_ctx {
     DevBuf b_indptr, b_col, b_val;
     bool active_is_base = true;
     i64 n = 0, m = 0, nnz = 0;
-    DevBuf a_indptr, a_col, a_val, rowidx;
+    DevBuf a_indptr, a_col, a_val;
     const int *indptr = nullptr, *col = nullptr;
     const float *val = nullptr;
-    bool rowidx_valid = false;
+    struct RowIndex : Derived<RowIndex> { DevBuf ids; } rowidx;   // COO row ids of the active matrix
 
-    // CSC copy + column items
-    bool csc_valid = false;
-    int seg = 256, seg_override = 0, struct_lpn = 0;   // column item length: adaptive unless PLSA_COL_SEG is set
-    i64 n_items = 0;
-    DevBuf colptr, csc_row, csc_val, csc_pos, item_first, item_col, item_start, item_order, partial, heavy_cols;
+    // CSC copy + column items + the columns with heavy_items items or more (Zipf head words) + the column pass' XCD stretches
+    struct Csc : Derived<Csc> {
+        DevBuf colptr, row, val, pos, item_first, item_col, item_start, item_end, item_order, heavy_cols;
+        DevBuf item_rec;             // visiting-order item records
+        DevBuf xcd_lo;               // chunk boundaries per XCD (measured, see ensure_balance)
+        bool balanced = false;       // xcd_lo matches the current structure
+        int seg = 256, n_heavy = 0;  // column item length
+        i64 n_items = 0;
+    } csc;
+    int seg_override = 0, struct_lpn = 0;   // column item length: adaptive unless PLSA_COL_SEG is set
+    DevBuf partial;
     bool use_item_order = true, xcd_split = true;
     // packed entry streams of the fused passes (plsa_kernels.hpp: Packed): pk_csr parallel to col / val, pk_csc parallel to
-    // csc_row / csc_val.  A stream is used (pk_*_ok) when its ids fit 24 bits and at most 1/16 of the entries escape.
+    // csc.row / csc.val.  A stream is used (ok) when its ids fit 24 bits and at most 1/16 of the entries escape.
     bool packed = true;              // PLSA_PACKED=0: the two-array streams everywhere (A/B)
-    bool pk_csr_valid = false, pk_csr_ok = false, pk_csc_valid = false, pk_csc_ok = false;
-    DevBuf pk_csr, pk_csc, pk_count;
+    struct PackedStream : Derived<PackedStream> { DevBuf buf; bool ok = false; } pk_csr, pk_csc;
+    DevBuf pk_count;
     int chunks_per_lane = 2;
     int row_lpn = 1, row_ch = 1;     // lane shape of the DOCUMENT pass (may differ from lpn / ch: see set_shape)
     bool row_shape_8x2 = true;       // PLSA_ROW_SHAPE=0: document pass in the common shape
-    bool p_borrowed = false;       // P(z|w,d) lives in memory lent by plsa_p_borrow (never freed, never re-allocated here)
     bool p_lent = false;           // plsa_p_reserve handed this context's P(z|w,d) address out: it must not move (no regrowth) until plsa_release_scratch
     int e_rows = -1;               // E-step traversal: 1 document-owned, 0 one group per non-zero, -1 by size (PLSA_E_ROWS)
     int mt_streams = 256;          // pieces the MT19937 init stream is cut into (PLSA_MT_STREAMS; 1 = sequential)
     i64 mt_min_blocks = 4096;      // ... once it is at least this many 624-word blocks long (PLSA_MT_MIN_BLOCKS)
-    int heavy_items = 32, n_heavy = 0;
+    int heavy_items = 32;
 
     // row items (documents cut into pieces) for corpora with few / very uneven rows
     bool force_wide = false;           // PLSA_FORCE_WIDE: 64-bit gather addresses whatever the table size
-    bool ritems_valid = false, use_ritems = false;
-    int rseg = 64, rseg_override = 0, ritems_mode = -1;   // ritems_mode: -1 auto, 0 never, 1 always (PLSA_ROW_ITEMS); rseg: entries per row item (PLSA_ROW_SEG, 0 = by size)
-    i64 n_ritems = 0;
-    DevBuf ritem_first, ritem_row, ritem_start, rpartial;
+    struct RowItems : Derived<RowItems> {
+        DevBuf first, row, start;
+        bool use = false;
+        int seg = 64;                // entries per row item
+        i64 n = 0;
+    } ritems;
+    int rseg_override = 0, ritems_mode = -1;   // ritems_mode: -1 auto, 0 never, 1 always (PLSA_ROW_ITEMS); PLSA_ROW_SEG (0 = by size)
+    DevBuf rpartial;
 
-    // items of the document-owned E-step: documents cut into pieces of eseg entries (balanced: the four
+    // items of the document-owned E-step: documents cut into pieces of seg entries (balanced: the four
     // groups of a wave all run the same number of gather/store bursts; measured 5.27 -> 4.62 ms at config 3)
-    bool eitems_valid = false;
-    int eseg = 0, eseg_override = -1;      // PLSA_E_SEG: -1 auto, 0 whole documents, N pieces of N entries
-    i64 n_eitems = 0;
-    DevBuf eitem_row, eitem_start;
+    struct EItems : Derived<EItems> { DevBuf row, start; int seg = 0; i64 n = 0; } eitems;
+    int eseg_override = -1;          // PLSA_E_SEG: -1 auto, 0 whole documents, N pieces of N entries
 
     // rows in descending-length order (row-owned kernels: groups of a wave finish together)
-    bool sort_rows = true, roworder_valid = false;
-    DevBuf row_order;
+    bool sort_rows = true;
+    struct RowOrder : Derived<RowOrder> {
+        DevBuf ids;
+        int range = 0;               // documents per range the order was built for (0: plain length order)
+    } roworder;
     // parameters of the last topical corpus generated on this context (plsa_synthetic_dominant_topics)
     i64 syn_n = 0; int syn_k0 = 0; double syn_alpha = 0.0; uint64_t syn_seed = 0;
     bool row_xcd = false;            // PLSA_ROW_XCD=1 (experiment): XCD x walks the x-th eighth of the documents (k_row_pass)
-    int roworder_range = 0;          // documents per range the current row_order was built for (0: plain length order)
 
     // factors
     int k = 0, kp = 0, lpn = 1, ch = 1;
     DevBuf U[3], Vt[3], Vacc;      // [2]: third buffers of the speculating fit loop (plsa_fit); cu, cv stay in {0, 1} outside it
     bool rot3 = false;             // inside that loop: the output buffers are (cu + 1) % 3, (cv + 1) % 3
     int speculate = -1;            // PLSA_SPECULATE: -1 small corpora only, 0 never, 1 whenever the loop allows
-    hipEvent_t ev_ll = nullptr;    // likelihood of a test has reached the host buffer
+    Event ev_ll;                   // likelihood of a test has reached the host buffer
     int cu = 0, cv = 0;
     i64 fac_n = 0, fac_m = 0;
-    DevBuf P;
+    DevBuf P;                      // borrowed while it lives in memory lent by plsa_p_borrow
+    struct PState : Derived<PState> {} p_state;   // P holds the responsibilities of the current factors (or plsa_set_p's)
     // arithmetic of the kernel-level operators and drivers (plsa_set_arithmetic; PLSA_REFERENCE_SUMS / PLSA_REFERENCE_LL of plsa_fit):
     // ref_sums: every factor sum one float32 accumulator in the reference's loop order (plsa_ref_kernels.hpp)
     // ref_ll:   the log-likelihood one float32 running sum over the non-zeros (plsa.py:322 read literally)
@@ -149,22 +205,23 @@ struct plsa_ctx {
     // quarter of the chunks of an iteration took the walk's slow way -- chains that drift too far from the real sums)
     int ref_chain_mode = 0;        // 0 auto, 1 always pairs, 2 always the serial chain
     bool ref_pairs_off = false;    // auto mode: the current corpus went back to the serial chain
-    DevBuf ref_csum, ref_pairs, ref_exps, ref_pairs2, ref_exps2, ref_stats, ref_ll_neg, ref_heavy, ref_tsum;
+    DevBuf ref_csum, ref_pairs, ref_exps, ref_pairs2, ref_exps2, ref_stats, ref_ll_neg;
     // tile sums of x * P(z|w,d) [* sw] left by the last reference-arithmetic E-step (valid for THAT P and THOSE weights only)
-    bool ref_tsum_valid = false;
-    const float *ref_tsum_sw = nullptr, *ref_e_sw = nullptr;   // weights the sums were formed with / the next E-step should use
-    int ref_tsum_tj = 0;
+    struct RefTileSums : Derived<RefTileSums> {
+        DevBuf sums;
+        const float *sw = nullptr;   // weights the sums were formed with
+        int tj = 0;                  // entries per tile
+    } ref_tsum;
+    const float *ref_e_sw = nullptr; // weights the next E-step should form its tile sums with
     bool ref_e_no_sums = false;      // the E-steps of a refit: no norm_pwz chain follows
-    bool ref_heavy_valid = false;
-    int n_ref_heavy = 0, ref_heavy_min = 0;
-    unsigned long long *h_ref_stats = nullptr;   // pinned [2]: chunks that took the slow way / chunks, of the last finished walk
-    hipEvent_t ev_ref_stats = nullptr;
+    struct RefHeavy : Derived<RefHeavy> { DevBuf cols; int n = 0, min = 0; } ref_heavy;   // the reference arithmetic's long columns: [count, columns...]
+    Pinned<unsigned long long> h_ref_stats;   // [2]: chunks that took the slow way / chunks, of the last finished walk
+    Event ev_ref_stats;
     bool ref_stats_pending = false;
     unsigned long long ref_slow_total = 0, ref_chunks_total = 0;   // accumulated over the walks read back so far (plsa_reference_chain_info)
     int placement_candidates = 4, placement_tried = 0;
     double placement_gbps[2] = {0.0, 0.0};
     size_t p_shift = 0;   // experiment knob: byte offset of P inside its allocation (PLSA_P_OFFSET_KB)
-    bool p_valid = false;
 
     // small buffers
     DevBuf sw, ll_partials, ll_out, colsum_partials, norm_pwz, norm_pdz, tmp0, tmp1, tmp2, cubtmp;
@@ -172,16 +229,14 @@ struct plsa_ctx {
     bool mt_chain = false;                        // PLSA_MT_CHAIN
     DevBuf mt_words, mt_state, mt_fin, mt_poly;   // MT19937 initialisation scratch: kept between calls (an ensemble member per call:
                                                   // four hipMalloc + four hipFree per member cost more than the generator kernels)
-    double *h_ll = nullptr;  // pinned
+    Pinned<double> h_ll;
 
-    DevBuf item_end, colsum_rows, colsum_rows2;
-    // column-pass schedule: visiting-order item records, chunk boundaries per XCD (measured, see ensure_balance)
-    DevBuf item_rec, xcd_lo, t_end;
+    DevBuf colsum_rows, colsum_rows2;
+    DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
     int order_band = -1;             // PLSA_ORDER_BAND: documents per band of the visiting order (-1 auto, 0 first-document order)
     int balance = -1;                // PLSA_BALANCE: -1 auto (large problems), 0 equal stretches, 1 always measure
-    bool bal_valid = false;          // xcd_lo matches the current structure
     bool bal_have_frac = false;      // bal_frac holds measured boundaries (kept across bootstrap resamples as the start)
     double bal_frac[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int bal_lo[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -200,14 +255,14 @@ struct plsa_ctx {
     i64 sw_n = 0;               // (their own buffer: a call that passes explicit weights stages them in c->sw and leaves these alone)
     DevBuf sw_res;
     DevBuf comm_send, comm_recv, comm_small, comm_stack;   // comm_stack: the member stack (plsa_stack_reserve)
-    float *comm_host = nullptr;      // pinned landing buffer of plsa_comm_allgather_stack
+    Pinned<float> comm_host;         // landing buffer of plsa_comm_allgather_stack
     size_t comm_host_cap = 0;
 
     // timing
     bool timing = false;
     std::vector<std::string> names;
     std::vector<Timed> timed;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     std::vector<double> acc_ms;
     std::vector<i64> acc_n;
 };
@@ -286,8 +341,8 @@ int ensure_best_placement(plsa_ctx *c, DevBuf &b, size_t bytes, int max_candidat
     if (ncand < 2 || bytes < ((size_t)256 << 20)) return ensure(c, b, bytes);
     std::vector<void *> cand;
     std::vector<float> ms;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    Event e0, e1;
+    (void)hipEventCreate(&e0.h); (void)hipEventCreate(&e1.h);
     const i64 n4 = (i64)(bytes / 16);
     const int grid = grid_for(c, n4, 256);
     for (int i = 0; i < ncand; ++i) {
@@ -304,7 +359,6 @@ int ensure_best_placement(plsa_ctx *c, DevBuf &b, size_t bytes, int max_candidat
         (void)hipEventElapsedTime(&t, e0, e1);
         ms.push_back(t / 2.f);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (cand.empty()) return ensure(c, b, bytes);
     size_t best = 0, worst = 0;
     for (size_t i = 1; i < cand.size(); ++i) { if (ms[i] < ms[best]) best = i; if (ms[i] > ms[worst]) worst = i; }
@@ -432,12 +486,6 @@ int copy_to_host(plsa_ctx *c, void *host, const void *dev, size_t bytes) {
     return 0;
 }
 
-void release(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
 int name_id(plsa_ctx *c, const char *name) {
     for (size_t i = 0; i < c->names.size(); ++i)
         if (c->names[i] == name) return (int)i;
@@ -447,10 +495,10 @@ int name_id(plsa_ctx *c, const char *name) {
     return (int)c->names.size() - 1;
 }
 
-hipEvent_t get_event(plsa_ctx *c) {
-    if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
+Event get_event(plsa_ctx *c) {
+    Event e;
+    if (!c->pool.empty()) { e = std::move(c->pool.back()); c->pool.pop_back(); }
+    else (void)hipEventCreate(&e.h);
     return e;
 }
 
@@ -464,8 +512,8 @@ int timing_flush(plsa_ctx *c) {
         HIPCHK(c, hipEventElapsedTime(&ms, t.a, t.b));
         c->acc_ms[t.name_id] += ms;
         c->acc_n[t.name_id] += 1;
-        c->pool.push_back(t.a);
-        c->pool.push_back(t.b);
+        c->pool.push_back(std::move(t.a));
+        c->pool.push_back(std::move(t.b));
     }
     c->timed.clear();
     return 0;
@@ -486,9 +534,16 @@ struct Scope {  // brackets one kernel launch with events when timing is on
     ~Scope() {
         if (on) {
             (void)hipEventRecord(t.b, c->ls);
-            c->timed.push_back(t);
+            c->timed.push_back(std::move(t));
         }
     }
+};
+
+struct LaunchOn {  // the kernel wrappers launch on `s` inside this scope (c->ls), on the previous stream again after it
+    plsa_ctx *c;
+    hipStream_t prev;
+    LaunchOn(plsa_ctx *c_, hipStream_t s) : c(c_), prev(c_->ls) { c->ls = s; }
+    ~LaunchOn() { c->ls = prev; }
 };
 
 template <class Fn>
@@ -560,29 +615,21 @@ void set_active_pointers(plsa_ctx *c) {
     } else {
         c->indptr = c->a_indptr.as<int>(); c->col = c->a_col.as<int>(); c->val = c->a_val.as<float>();
     }
-    c->rowidx_valid = false;
-    c->csc_valid = false;
-    c->pk_csr_valid = false;
-    c->pk_csc_valid = false;
-    c->roworder_valid = false;
-    c->ritems_valid = false;
-    c->eitems_valid = false;
-    c->p_valid = false;
+    c->rowidx.invalidate(); c->csc.invalidate(); c->pk_csr.invalidate(); c->pk_csc.invalidate(); c->roworder.invalidate();
+    c->ritems.invalidate(); c->eitems.invalidate(); c->p_state.invalidate(); c->ref_heavy.invalidate(); c->ref_tsum.invalidate();
     c->ref_pairs_off = false;
-    c->ref_heavy_valid = false;
-    c->ref_tsum_valid = false;
 }
 
 int ensure_rowidx(plsa_ctx *c) {
-    if (c->rowidx_valid) return 0;
-    CHK(ensure(c, c->rowidx, sizeof(int) * (size_t)c->nnz));
+    if (c->rowidx.valid) return 0;
+    CHK(ensure(c, c->rowidx.ids, sizeof(int) * (size_t)c->nnz));
     if (c->n > 0) {
         Scope s(c, "k_expand_rows");
         hipLaunchKernelGGL(plsa::k_expand_rows, dim3(grid_for(c, c->n, 4)), dim3(256), 0, c->stream,
-                           c->indptr, (int)c->n, c->rowidx.as<int>());
+                           c->indptr, (int)c->n, c->rowidx.ids.as<int>());
     }
     CHK(launch_check(c, "k_expand_rows"));
-    c->rowidx_valid = true;
+    c->rowidx.valid = true;
     return 0;
 }
 
@@ -598,10 +645,10 @@ int ensure_roworder(plsa_ctx *c, const int **out) {
     *out = nullptr;
     if (!c->sort_rows) return 0;
     const int range = row_xcd_range(c);
-    if (!c->roworder_valid || c->roworder_range != range) {
-        c->roworder_range = range;
+    if (!c->roworder.valid || c->roworder.range != range) {
+        c->roworder.range = range;
         const i64 n = c->n;
-        CHK(ensure(c, c->row_order, sizeof(int) * (size_t)n));
+        CHK(ensure(c, c->roworder.ids, sizeof(int) * (size_t)n));
         CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)n * 2));
         CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)n));
         int *len = c->tmp0.as<int>(), *len_sorted = c->tmp0.as<int>() + n, *ids = c->tmp1.as<int>();
@@ -610,13 +657,13 @@ int ensure_roworder(plsa_ctx *c, const int **out) {
         CHK(launch_check(c, "k_row_lengths"));
         size_t bytes = 0;
         HIPCHK(c, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, len, len_sorted, ids,
-                                                               c->row_order.as<int>(), (int)n, 0, 32, c->stream));
+                                                               c->roworder.ids.as<int>(), (int)n, 0, 32, c->stream));
         CHK(ensure(c, c->cubtmp, bytes));
         HIPCHK(c, hipcub::DeviceRadixSort::SortPairsDescending(c->cubtmp.p, bytes, len, len_sorted, ids,
-                                                               c->row_order.as<int>(), (int)n, 0, 32, c->stream));
-        c->roworder_valid = true;
+                                                               c->roworder.ids.as<int>(), (int)n, 0, 32, c->stream));
+        c->roworder.valid = true;
     }
-    *out = c->row_order.as<int>();
+    *out = c->roworder.ids.as<int>();
     return 0;
 }
 
@@ -625,7 +672,7 @@ int exclusive_sum_int(plsa_ctx *c, const int *in, int *out, i64 count);
 // Decide whether the document pass should run over row items, and build them.  Row ownership needs
 // enough rows to fill 256 CUs x 32 waves x (64/LPN) groups, and rows of comparable length.
 int ensure_ritems(plsa_ctx *c) {
-    if (c->ritems_valid) return 0;
+    if (c->ritems.valid) return 0;
     const i64 n = c->n;
     const i64 group_slots = (i64)c->prop.multiProcessorCount * 32 * (64 / std::max(1, c->row_lpn));
     const double avg = (double)c->nnz / (double)std::max<i64>(n, 1);
@@ -635,43 +682,43 @@ int ensure_ritems(plsa_ctx *c) {
     // kernels of round 4 row items of 16 / 24 / 32 / 40 / 48 / 64 entries give 9.9 / 10.7 / 11.1 / 11.1 / 10.9 / 10.4 k
     // iterations/s at config 1, profiles/r04_small_corpus_item_lengths.txt)
     const int rseg_decide = c->rseg_override ? c->rseg_override : 64;
-    c->use_ritems = c->ritems_mode == 1 || (c->ritems_mode < 0 && n < 2 * group_slots && avg > 2.0 * rseg_decide);
-    if (c->rseg_override) c->rseg = c->rseg_override;
+    c->ritems.use = c->ritems_mode == 1 || (c->ritems_mode < 0 && n < 2 * group_slots && avg > 2.0 * rseg_decide);
+    if (c->rseg_override) c->ritems.seg = c->rseg_override;
     else {
         const i64 per_slot = c->nnz / std::max<i64>(group_slots, 1);
         int r = 16;
         while (r * 2 <= per_slot && r < 64) r *= 2;
-        c->rseg = r;
+        c->ritems.seg = r;
     }
-    c->n_ritems = 0;
-    if (c->use_ritems) {
-        CHK(ensure(c, c->ritem_first, sizeof(int) * (size_t)(n + 1)));
+    c->ritems.n = 0;
+    if (c->ritems.use) {
+        CHK(ensure(c, c->ritems.first, sizeof(int) * (size_t)(n + 1)));
         CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)(n + 1)));
         HIPCHK(c, hipMemsetAsync(c->tmp0.p, 0, sizeof(int) * (size_t)(n + 1), c->stream));
         hipLaunchKernelGGL(plsa::k_item_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, (int)n, c->rseg, c->tmp0.as<int>());
-        CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->ritem_first.as<int>(), n + 1));
+                           c->indptr, (int)n, c->ritems.seg, c->tmp0.as<int>());
+        CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->ritems.first.as<int>(), n + 1));
         int cnt = 0;
-        HIPCHK(c, hipMemcpyAsync(&cnt, c->ritem_first.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&cnt, c->ritems.first.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->n_ritems = cnt;
-        CHK(ensure(c, c->ritem_row, sizeof(int) * (size_t)std::max(cnt, 1)));
-        CHK(ensure(c, c->ritem_start, sizeof(int) * (size_t)std::max(cnt, 1)));
+        c->ritems.n = cnt;
+        CHK(ensure(c, c->ritems.row, sizeof(int) * (size_t)std::max(cnt, 1)));
+        CHK(ensure(c, c->ritems.start, sizeof(int) * (size_t)std::max(cnt, 1)));
         hipLaunchKernelGGL(plsa::k_ritem_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, c->ritem_first.as<int>(), (int)n, c->rseg, c->ritem_row.as<int>(),
-                           c->ritem_start.as<int>());
+                           c->indptr, c->ritems.first.as<int>(), (int)n, c->ritems.seg, c->ritems.row.as<int>(),
+                           c->ritems.start.as<int>());
         CHK(launch_check(c, "k_ritem_fill"));
     }
-    c->ritems_valid = true;
+    c->ritems.valid = true;
     return 0;
 }
 
 // items of the document-owned E-step (its own piece length, independent of the document pass' row items)
 int ensure_eitems(plsa_ctx *c, int eseg) {
-    if (c->eitems_valid && c->eseg == eseg) return 0;
+    if (c->eitems.valid && c->eitems.seg == eseg) return 0;
     const i64 n = c->n;
-    c->eseg = eseg;
-    c->n_eitems = 0;
+    c->eitems.seg = eseg;
+    c->eitems.n = 0;
     if (eseg > 0) {
         CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)(n + 1)));
         CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)(n + 1)));
@@ -682,15 +729,15 @@ int ensure_eitems(plsa_ctx *c, int eseg) {
         int cnt = 0;
         HIPCHK(c, hipMemcpyAsync(&cnt, c->tmp1.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->n_eitems = cnt;
-        CHK(ensure(c, c->eitem_row, sizeof(int) * (size_t)std::max(cnt, 1)));
-        CHK(ensure(c, c->eitem_start, sizeof(int) * (size_t)std::max(cnt, 1)));
+        c->eitems.n = cnt;
+        CHK(ensure(c, c->eitems.row, sizeof(int) * (size_t)std::max(cnt, 1)));
+        CHK(ensure(c, c->eitems.start, sizeof(int) * (size_t)std::max(cnt, 1)));
         hipLaunchKernelGGL(plsa::k_ritem_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, c->tmp1.as<int>(), (int)n, eseg, c->eitem_row.as<int>(), c->eitem_start.as<int>());
+                           c->indptr, c->tmp1.as<int>(), (int)n, eseg, c->eitems.row.as<int>(), c->eitems.start.as<int>());
         CHK(launch_check(c, "k_ritem_fill"));
         HIPCHK(c, hipStreamSynchronize(c->stream));      // tmp1 is reused by other structure builds
     }
-    c->eitems_valid = true;
+    c->eitems.valid = true;
     return 0;
 }
 
@@ -703,7 +750,7 @@ int exclusive_sum_int(plsa_ctx *c, const int *in, int *out, i64 count) {
 }
 
 int ensure_csc(plsa_ctx *c) {
-    if (c->csc_valid) return 0;
+    if (c->csc.valid) return 0;
     CHK(ensure_rowidx(c));
     {   // item length: a group walks seg/LPN dependent gather batches per item, so small problems want
         // short items (enough items to fill the chip: config 1 0.244 -> 0.094 ms at 16) and large
@@ -722,21 +769,21 @@ int ensure_csc(plsa_ctx *c) {
         // long items for the Zipf-head words only (256 entries, the others 64) cost 1.96 -> 3.0 ms at config 3
         const int cap = 64;
         while (seg * 2 <= want && seg < cap) seg *= 2;
-        c->seg = c->seg_override ? c->seg_override : seg;
+        c->csc.seg = c->seg_override ? c->seg_override : seg;
     }
     const i64 nnz = c->nnz, m = c->m;
-    CHK(ensure(c, c->colptr, sizeof(int) * (size_t)(m + 1)));
-    CHK(ensure(c, c->csc_row, sizeof(int) * (size_t)nnz));
-    CHK(ensure(c, c->csc_val, sizeof(float) * (size_t)nnz));
-    CHK(ensure(c, c->csc_pos, sizeof(int) * (size_t)nnz));
+    CHK(ensure(c, c->csc.colptr, sizeof(int) * (size_t)(m + 1)));
+    CHK(ensure(c, c->csc.row, sizeof(int) * (size_t)nnz));
+    CHK(ensure(c, c->csc.val, sizeof(float) * (size_t)nnz));
+    CHK(ensure(c, c->csc.pos, sizeof(int) * (size_t)nnz));
     CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)std::max<i64>(nnz, m + 1)));  // counts, then sorted keys
     CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)nnz));                         // iota
     // the column pass' packed stream is written by the same gather (documents are its ids)
     const bool pack = c->packed && nnz > 0 && c->n <= plsa::PACK_MAX_IDS;
-    c->pk_csc_valid = false;
-    c->pk_csc_ok = false;
+    c->pk_csc.invalidate();
+    c->pk_csc.ok = false;
     if (pack) {
-        CHK(ensure(c, c->pk_csc, sizeof(unsigned) * (size_t)nnz));
+        CHK(ensure(c, c->pk_csc.buf, sizeof(unsigned) * (size_t)nnz));
         CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
         HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
     }
@@ -748,38 +795,38 @@ int ensure_csc(plsa_ctx *c) {
         while (((i64)1 << bits) < m) ++bits;
         size_t bytes = 0;
         HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->col, c->tmp0.as<int>(),
-                                                     c->tmp1.as<int>(), c->csc_pos.as<int>(), nnz, 0,
+                                                     c->tmp1.as<int>(), c->csc.pos.as<int>(), nnz, 0,
                                                      bits, c->stream));
         CHK(ensure(c, c->cubtmp, bytes));
         HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, bytes, c->col, c->tmp0.as<int>(),
-                                                     c->tmp1.as<int>(), c->csc_pos.as<int>(), nnz, 0,
+                                                     c->tmp1.as<int>(), c->csc.pos.as<int>(), nnz, 0,
                                                      bits, c->stream));
         hipLaunchKernelGGL(plsa::k_colptr_from_sorted, dim3((unsigned)((m + 256) / 256)), dim3(256), 0, c->stream,
-                           c->tmp0.as<int>(), nnz, (int)m, c->colptr.as<int>());
+                           c->tmp0.as<int>(), nnz, (int)m, c->csc.colptr.as<int>());
         hipLaunchKernelGGL(plsa::k_csc_gather, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
-                           c->csc_pos.as<int>(), c->rowidx.as<int>(), c->val, nnz,
-                           c->csc_row.as<int>(), c->csc_val.as<float>(), pack ? c->pk_csc.as<unsigned>() : nullptr,
+                           c->csc.pos.as<int>(), c->rowidx.ids.as<int>(), c->val, nnz,
+                           c->csc.row.as<int>(), c->csc.val.as<float>(), pack ? c->pk_csc.buf.as<unsigned>() : nullptr,
                            pack ? c->pk_count.as<unsigned long long>() : nullptr);
         CHK(launch_check(c, "k_csc_gather"));
     } else {
-        HIPCHK(c, hipMemsetAsync(c->colptr.p, 0, sizeof(int) * (size_t)(m + 1), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->csc.colptr.p, 0, sizeof(int) * (size_t)(m + 1), c->stream));
     }
     // column items
-    CHK(ensure(c, c->item_first, sizeof(int) * (size_t)(m + 1)));
+    CHK(ensure(c, c->csc.item_first, sizeof(int) * (size_t)(m + 1)));
     HIPCHK(c, hipMemsetAsync(c->tmp0.p, 0, sizeof(int) * (size_t)(m + 1), c->stream));
     hipLaunchKernelGGL(plsa::k_col_item_counts, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream,
-                       c->colptr.as<int>(), (int)m, c->seg, c->tmp0.as<int>());
-    CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->item_first.as<int>(), m + 1));
+                       c->csc.colptr.as<int>(), (int)m, c->csc.seg, c->tmp0.as<int>());
+    CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->csc.item_first.as<int>(), m + 1));
     int n_items = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_items, c->item_first.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost,
+    HIPCHK(c, hipMemcpyAsync(&n_items, c->csc.item_first.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->n_items = n_items;
+    c->csc.n_items = n_items;
     const size_t ni = (size_t)std::max<i64>(n_items, 1);
-    CHK(ensure(c, c->item_col, sizeof(int) * ni));
-    CHK(ensure(c, c->item_start, sizeof(int) * ni));
-    CHK(ensure(c, c->item_end, sizeof(int) * ni));
-    CHK(ensure(c, c->item_order, sizeof(int) * ni));
+    CHK(ensure(c, c->csc.item_col, sizeof(int) * ni));
+    CHK(ensure(c, c->csc.item_start, sizeof(int) * ni));
+    CHK(ensure(c, c->csc.item_end, sizeof(int) * ni));
+    CHK(ensure(c, c->csc.item_order, sizeof(int) * ni));
     CHK(ensure(c, c->tmp2, sizeof(unsigned long long) * ni * 2));   // sort keys, sorted keys
     CHK(ensure(c, c->tmp1, sizeof(int) * ni));           // item ids
     unsigned long long *d_key = c->tmp2.as<unsigned long long>();
@@ -797,42 +844,42 @@ int ensure_csc(plsa_ctx *c) {
     if (band > 0) { i64 n_bands = c->n / band + 1; int bb = 1; while (((i64)1 << bb) < n_bands) ++bb; key_bits = len_bits + bb; }
     if (n_items > 0)
         hipLaunchKernelGGL(plsa::k_item_fill, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream,
-                           c->colptr.as<int>(), c->item_first.as<int>(), (int)m, c->seg, c->csc_row.as<int>(),
-                           c->item_col.as<int>(), c->item_start.as<int>(), c->item_end.as<int>(), band, len_bits, d_key,
+                           c->csc.colptr.as<int>(), c->csc.item_first.as<int>(), (int)m, c->csc.seg, c->csc.row.as<int>(),
+                           c->csc.item_col.as<int>(), c->csc.item_start.as<int>(), c->csc.item_end.as<int>(), band, len_bits, d_key,
                            c->tmp1.as<int>(), n_items);
     CHK(launch_check(c, "k_item_fill"));
     if (n_items > 0) {   // visiting order: band-major, Zipf-head words first inside a band (stable)
         size_t bytes = 0;
         HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_key, d_key + ni,
-                                                     c->tmp1.as<int>(), c->item_order.as<int>(), n_items, 0, key_bits, c->stream));
+                                                     c->tmp1.as<int>(), c->csc.item_order.as<int>(), n_items, 0, key_bits, c->stream));
         CHK(ensure(c, c->cubtmp, bytes));
         HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, bytes, d_key, d_key + ni,
-                                                     c->tmp1.as<int>(), c->item_order.as<int>(), n_items, 0, key_bits, c->stream));
+                                                     c->tmp1.as<int>(), c->csc.item_order.as<int>(), n_items, 0, key_bits, c->stream));
     }
     // visiting-order records (one 16-byte load per item instead of an index chain)
-    CHK(ensure(c, c->item_rec, sizeof(int4) * ni));
+    CHK(ensure(c, c->csc.item_rec, sizeof(int4) * ni));
     if (n_items > 0) {
         hipLaunchKernelGGL(plsa::k_item_records, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream,
-                           c->use_item_order ? c->item_order.as<int>() : nullptr, c->item_col.as<int>(),
-                           c->item_start.as<int>(), c->item_end.as<int>(), (i64)n_items, c->item_rec.as<int4>());
+                           c->use_item_order ? c->csc.item_order.as<int>() : nullptr, c->csc.item_col.as<int>(),
+                           c->csc.item_start.as<int>(), c->csc.item_end.as<int>(), (i64)n_items, c->csc.item_rec.as<int4>());
         CHK(launch_check(c, "k_item_records"));
     }
-    c->bal_valid = false;
+    c->csc.balanced = false;
     // columns whose item count makes a single group's serial reduction a tail (Zipf head words)
-    CHK(ensure(c, c->heavy_cols, sizeof(int) * (size_t)(m + 1)));
-    HIPCHK(c, hipMemsetAsync(c->heavy_cols.as<int>() + m, 0, sizeof(int), c->stream));
+    CHK(ensure(c, c->csc.heavy_cols, sizeof(int) * (size_t)(m + 1)));
+    HIPCHK(c, hipMemsetAsync(c->csc.heavy_cols.as<int>() + m, 0, sizeof(int), c->stream));
     hipLaunchKernelGGL(plsa::k_heavy_list, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream,
-                       c->item_first.as<int>(), (int)m, c->heavy_items, c->heavy_cols.as<int>(),
-                       c->heavy_cols.as<int>() + m);
+                       c->csc.item_first.as<int>(), (int)m, c->heavy_items, c->csc.heavy_cols.as<int>(),
+                       c->csc.heavy_cols.as<int>() + m);
     CHK(launch_check(c, "k_heavy_list"));
-    HIPCHK(c, hipMemcpyAsync(&c->n_heavy, c->heavy_cols.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->csc.n_heavy, c->csc.heavy_cols.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     unsigned long long escaped = 0;
     if (pack) HIPCHK(c, hipMemcpyAsync(&escaped, c->pk_count.p, sizeof escaped, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->csc_valid = true;
-    c->pk_csc_valid = c->packed;
-    c->pk_csc_ok = pack && escaped * 16 <= (unsigned long long)nnz;
-    if (!c->pk_csc_ok) release(c->pk_csc);
+    c->csc.valid = true;
+    c->pk_csc.valid = c->packed;
+    c->pk_csc.ok = pack && escaped * 16 <= (unsigned long long)nnz;
+    if (!c->pk_csc.ok) c->pk_csc.buf.release();
     return 0;
 }
 
@@ -842,7 +889,7 @@ int ensure_csc(plsa_ctx *c) {
 int build_packed(plsa_ctx *c, DevBuf &out, const int *ids, const float *vals, i64 id_range, bool *ok) {
     *ok = false;
     const i64 nnz = c->nnz;
-    if (nnz <= 0 || id_range > plsa::PACK_MAX_IDS) { release(out); return 0; }
+    if (nnz <= 0 || id_range > plsa::PACK_MAX_IDS) { out.release(); return 0; }
     CHK(ensure(c, out, sizeof(unsigned) * (size_t)nnz));
     CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
     HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
@@ -853,24 +900,24 @@ int build_packed(plsa_ctx *c, DevBuf &out, const int *ids, const float *vals, i6
     HIPCHK(c, hipMemcpyAsync(&escaped, c->pk_count.p, sizeof escaped, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *ok = escaped * 16 <= (unsigned long long)nnz;
-    if (!*ok) release(out);
+    if (!*ok) out.release();
     return 0;
 }
 
 // the document pass' packed stream: built on the first fused pass after an upload / bootstrap / generate
 int ensure_packed_csr(plsa_ctx *c) {
-    if (!c->packed || c->pk_csr_valid) return 0;
-    CHK(build_packed(c, c->pk_csr, c->col, c->val, c->m, &c->pk_csr_ok));
-    c->pk_csr_valid = true;
+    if (!c->packed || c->pk_csr.valid) return 0;
+    CHK(build_packed(c, c->pk_csr.buf, c->col, c->val, c->m, &c->pk_csr.ok));
+    c->pk_csr.valid = true;
     return 0;
 }
 
 // the column pass' packed stream: written by ensure_csc; rebuilt from the CSC arrays after plsa_release_scratch
 int ensure_packed_csc(plsa_ctx *c) {
     CHK(ensure_csc(c));
-    if (!c->packed || c->pk_csc_valid) return 0;
-    CHK(build_packed(c, c->pk_csc, c->csc_row.as<int>(), c->csc_val.as<float>(), c->n, &c->pk_csc_ok));
-    c->pk_csc_valid = true;
+    if (!c->packed || c->pk_csc.valid) return 0;
+    CHK(build_packed(c, c->pk_csc.buf, c->csc.row.as<int>(), c->csc.val.as<float>(), c->n, &c->pk_csc.ok));
+    c->pk_csc.valid = true;
     return 0;
 }
 
@@ -914,9 +961,9 @@ void set_shape(plsa_ctx *c, int k) {
     c->row_lpn = c->lpn; c->row_ch = c->ch;
     if (c->row_shape_8x2 && c->lpn == 16 && c->ch == 1 && kp == 64) { c->row_lpn = 8; c->row_ch = 2; }
     if (lpn != prev_lpn) {        // item lengths / the row-item decision depend on the lane shape
-        c->ritems_valid = false;
-        c->eitems_valid = false;
-        if (!c->seg_override) c->csc_valid = false;
+        c->ritems.invalidate();
+        c->eitems.invalidate();
+        if (!c->seg_override) c->csc.invalidate();
         c->struct_lpn = lpn;
     }
 }
@@ -942,20 +989,20 @@ int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_
 int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out);
 
 int run_e_step(plsa_ctx *c, float thresh) {
-    c->ref_tsum_valid = false;          // (a new P(z|w,d): the tile sums of the last reference-arithmetic E-step are history)
+    c->ref_tsum.invalidate();          // (a new P(z|w,d): the tile sums of the last reference-arithmetic E-step are history)
     {   // the materialised schedule needs the whole nnz x kp array: say so instead of a bare OOM
         const size_t need = sizeof(float) * (size_t)(c->nnz + 64) * (size_t)c->kp;
         size_t free_b = 0, total_b = 0;
-        if (!c->p_borrowed && c->P.cap < need && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + c->P.cap < need)
+        if (!c->P.borrowed && c->P.cap < need && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + c->P.cap < need)
             return fail(c, c->ref_sums ? "the reference arithmetic (PLSA_REFERENCE_SUMS) stores P(z|w,d) like the reference does: %.1f GB needed, "
                                          "%.1f GB of HBM free -- at this size only the default arithmetic is available"
                                        : "materialising P(z|w,d) needs %.1f GB but only %.1f GB of HBM are free; use the fused "
                            "schedule (PLSA_FUSED), which never stores it, or tile the documents (plsa_em_accumulate_materialised)", need / 1e9, (free_b + c->P.cap) / 1e9);
     }
-    if (c->p_borrowed || c->p_lent) {
+    if (c->P.borrowed || c->p_lent) {
         const size_t need = sizeof(float) * (size_t)(c->nnz + 64) * (size_t)c->kp;
         if (c->P.cap < need)
-            return fail(c, c->p_borrowed ? "the borrowed P(z|w,d) buffer holds %.2f GB, this matrix needs %.2f GB (plsa_p_borrow)"
+            return fail(c, c->P.borrowed ? "the borrowed P(z|w,d) buffer holds %.2f GB, this matrix needs %.2f GB (plsa_p_borrow)"
                                          : "the P(z|w,d) buffer lent out by plsa_p_reserve holds %.2f GB, this matrix needs %.2f GB: it cannot "
                                            "grow while other contexts hold its address (end the loans, then plsa_release_scratch)",
                         c->P.cap / 1e9, need / 1e9);
@@ -982,8 +1029,8 @@ int run_e_step(plsa_ctx *c, float thresh) {
         // (0.224 against 0.234-0.238 ms for 16-40 and 0.316 ms for whole documents at config 2)
         const int eseg = c->eseg_override >= 0 ? c->eseg_override : (c->lpn >= 16 ? 64 : (c->lpn == 8 ? 8 : 16));
         CHK(ensure_eitems(c, eseg));
-        const bool items = eseg > 0 && c->n_eitems > 0;
-        const int grid = grid_for(c, items ? c->n_eitems : c->n, 256 / c->lpn);
+        const bool items = eseg > 0 && c->eitems.n > 0;
+        const int grid = grid_for(c, items ? c->eitems.n : c->n, 256 / c->lpn);
         const int *order = nullptr;
         if (!items) CHK(ensure_roworder(c, &order));
         CHK(dispatch_shape(c, [&](auto S) {
@@ -991,8 +1038,8 @@ int run_e_step(plsa_ctx *c, float thresh) {
             auto go = [&](auto TN) {      // TN: the denormal-norm rescue is compiled in only for thresholds below TINY_THRESH
                 hipLaunchKernelGGL((plsa::k_e_step_rows<decltype(S), decltype(TN)::value>), dim3(grid), dim3(256), 0, c->stream,
                                    c->indptr, c->col, (int)c->n, order, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
-                                   p_base(c), c->kp, thresh, items ? c->eitem_row.as<int>() : nullptr,
-                                   items ? c->eitem_start.as<int>() : nullptr, eseg, c->n_eitems);
+                                   p_base(c), c->kp, thresh, items ? c->eitems.row.as<int>() : nullptr,
+                                   items ? c->eitems.start.as<int>() : nullptr, eseg, c->eitems.n);
             };
             if (thresh < plsa::TINY_THRESH) go(std::true_type{}); else go(std::false_type{});
         }));
@@ -1004,14 +1051,14 @@ int run_e_step(plsa_ctx *c, float thresh) {
             Scope s(c, "k_e_step");
             auto go = [&](auto TN) {
                 hipLaunchKernelGGL((plsa::k_e_step<decltype(S), decltype(TN)::value>), dim3(grid), dim3(256), 0, c->stream,
-                                   c->rowidx.as<int>(), c->col, c->nnz, c->U[c->cu].as<float>(),
+                                   c->rowidx.ids.as<int>(), c->col, c->nnz, c->U[c->cu].as<float>(),
                                    c->Vt[c->cv].as<float>(), p_base(c), c->kp, thresh);
             };
             if (thresh < plsa::TINY_THRESH) go(std::true_type{}); else go(std::false_type{});
         }));
     }
     CHK(launch_check(c, "k_e_step"));
-    c->p_valid = true;
+    c->p_state.valid = true;
     return 0;
 }
 
@@ -1019,8 +1066,8 @@ int run_e_step(plsa_ctx *c, float thresh) {
 int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, float thresh,
                  float *d_norm_pdz, int *ll_blocks) {
     CHK(ensure_ritems(c));
-    const bool items = c->use_ritems && c->n_ritems > 0;
-    int grid = grid_for(c, items ? c->n_ritems : c->n, 256 / c->row_lpn);
+    const bool items = c->ritems.use && c->ritems.n > 0;
+    int grid = grid_for(c, items ? c->ritems.n : c->n, 256 / c->row_lpn);
     const int *order = nullptr;
     // PLSA_ROW_XCD (experiment): one trip, grid a multiple of 8, XCD x takes the x-th eighth of the visiting list, which is
     // ordered range by range (range = the documents of one eighth), longest document first inside a range
@@ -1028,18 +1075,18 @@ int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, floa
     const bool xcd_rows = !items && !from_p && c->sort_rows && row_xcd_range(c) > 0;
     if (xcd_rows) grid = (int)(((c->n + gpb_row - 1) / gpb_row + 7) / 8 * 8);
     if (!items) CHK(ensure_roworder(c, &order));
-    if (items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->n_ritems * c->kp));
-    const int *ri_row = items ? c->ritem_row.as<int>() : nullptr;
-    const int *ri_start = items ? c->ritem_start.as<int>() : nullptr;
+    if (items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->ritems.n * c->kp));
+    const int *ri_row = items ? c->ritems.row.as<int>() : nullptr;
+    const int *ri_start = items ? c->ritems.start.as<int>() : nullptr;
     float *rpart = items ? c->rpartial.as<float>() : nullptr;
-    const int rseg = c->rseg;
-    const i64 n_ritems = c->n_ritems;
+    const int rseg = c->ritems.seg;
+    const i64 n_ritems = c->ritems.n;
     if (want_ll) CHK(ensure(c, c->ll_partials, sizeof(double) * (size_t)grid));
     if (!from_p) CHK(ensure_packed_csr(c));
-    const bool packed = !from_p && c->packed && c->pk_csr_ok;
+    const bool packed = !from_p && c->packed && c->pk_csr.ok;
     CHK(dispatch_shape_row(c, [&](auto S) {
         using Sh = decltype(S);
-        const int *ip = c->indptr, *cl = packed ? c->pk_csr.as<int>() : c->col;
+        const int *ip = c->indptr, *cl = packed ? c->pk_csr.buf.as<int>() : c->col;
         const float *vl = c->val, *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
         const float *P = p_base(c);
         float *Un = c->U[out_u(c)].as<float>();
@@ -1066,7 +1113,7 @@ int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, floa
         if (items) {
             Scope s(c, "k_row_reduce");
             hipLaunchKernelGGL((plsa::k_row_reduce<Sh>), dim3(grid_for(c, c->n, 256 / Sh::LPN)), dim3(256), 0, c->ls,
-                               c->ritem_first.as<int>(), n, rpart, Un, d_norm_pdz, kp);
+                               c->ritems.first.as<int>(), n, rpart, Un, d_norm_pdz, kp);
         }
     }));
     CHK(launch_check(c, "k_row_pass"));
@@ -1107,12 +1154,12 @@ int col_grid(plsa_ctx *c, int n_chunks, bool split) {
 // depend on the boundaries (partials are per item, norm_pwz rows per chunk), only the speed does.
 template <class Launch>
 int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
-    if (c->bal_valid && c->bal_chunks == n_chunks) return 0;
-    CHK(ensure(c, c->xcd_lo, sizeof(int) * 16));
+    if (c->csc.balanced && c->bal_chunks == n_chunks) return 0;
+    CHK(ensure(c, c->csc.xcd_lo, sizeof(int) * 16));
     const bool warm = c->bal_have_frac;
     if (!warm) for (int x = 0; x <= 8; ++x) c->bal_frac[x] = x / 8.0;
     balance_set_lo(c, n_chunks);
-    HIPCHK(c, hipMemcpyAsync(c->xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
+    HIPCHK(c, hipMemcpyAsync(c->csc.xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
     c->bal_launches = 0;
     // auto: corpora from ~1e8 cells per iteration (config 2: 4279 -> 4540 iterations/s; the tuning launches of a
     // 20NG-sized corpus would cost a bootstrap member more than they return)
@@ -1156,7 +1203,7 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
             if (it == max_launches - 1 && !warm) {   // out of launches: keep the best measured boundaries
                 for (int x = 0; x <= 8; ++x) c->bal_frac[x] = best_frac[x];
                 balance_set_lo(c, n_chunks);
-                HIPCHK(c, hipMemcpyAsync(c->xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
+                HIPCHK(c, hipMemcpyAsync(c->csc.xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
                 break;
             }
             double size[8], tot = 0.0;
@@ -1168,11 +1215,11 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
             for (int x = 0; x < 8; ++x) { acc += size[x]; c->bal_frac[x + 1] = acc / tot; }
             c->bal_frac[8] = 1.0;
             balance_set_lo(c, n_chunks);
-            HIPCHK(c, hipMemcpyAsync(c->xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
+            HIPCHK(c, hipMemcpyAsync(c->csc.xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
         }
         c->bal_have_frac = true;
     }
-    c->bal_valid = true;
+    c->csc.balanced = true;
     return 0;
 }
 
@@ -1182,13 +1229,13 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
 //        3 = both
 int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int parts = 3) {
     CHK(from_p ? ensure_csc(c) : ensure_packed_csc(c));
-    const bool packed = !from_p && c->packed && c->pk_csc_ok;
-    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->n_items, 1) * c->kp));
+    const bool packed = !from_p && c->packed && c->pk_csc.ok;
+    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->csc.n_items, 1) * c->kp));
     int rc = 0;
     CHK(dispatch_shape_gather(c, table_is_wide(c, c->n), [&](auto S) {     // the pass gathers P(z|d) rows: n of them
         using Sh = decltype(S);
         constexpr int LPN = Sh::LPN, GPB = 256 / LPN;
-        const i64 n_visit = c->n_items;
+        const i64 n_visit = c->csc.n_items;
         const int n_chunks = (int)((n_visit + GPB - 1) / GPB);
         const int grid2 = grid_for(c, c->m, GPB);
         // a P(z|d) table that fits every XCD's L2 (20NG shape: 1.5 MB) has no band to keep local: plain grid-stride
@@ -1205,10 +1252,10 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
                 if (c->small_grid > 0 && (double)c->nnz * c->kp < c->overlap_full_limit)
                     grid = std::min(grid, c->small_grid * c->prop.multiProcessorCount);
                 Scope s(c, from_p ? "k_col_pass<P>" : "k_col_pass<fused>");
-                const int4 *rec = c->item_rec.as<int4>();
-                const int *lo = c->xcd_lo.as<int>(), *cp = c->csc_pos.as<int>();
-                const int *cr = packed ? c->pk_csc.as<int>() : c->csc_row.as<int>();
-                const float *cvl = c->csc_val.as<float>(), *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
+                const int4 *rec = c->csc.item_rec.as<int4>();
+                const int *lo = c->csc.xcd_lo.as<int>(), *cp = c->csc.pos.as<int>();
+                const int *cr = packed ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
+                const float *cvl = c->csc.val.as<float>(), *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
                 float *part = c->partial.as<float>();
                 double *sums = c->colsum_rows.as<double>();
                 unsigned long long *te = c->t_end.as<unsigned long long>();
@@ -1241,9 +1288,9 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
         if (parts & 2) {
             // heavy columns (one block each) and the rest share one launch
             Scope s(c, "k_col_reduce");
-            hipLaunchKernelGGL((plsa::k_col_reduce<Sh>), dim3(grid2 + c->n_heavy), dim3(256),
+            hipLaunchKernelGGL((plsa::k_col_reduce<Sh>), dim3(grid2 + c->csc.n_heavy), dim3(256),
                                (256 / LPN) * c->kp * sizeof(float), c->ls,
-                               c->item_first.as<int>(), (int)c->m, c->heavy_items, c->heavy_cols.as<int>(), c->n_heavy,
+                               c->csc.item_first.as<int>(), (int)c->m, c->heavy_items, c->csc.heavy_cols.as<int>(), c->csc.n_heavy,
                                c->partial.as<float>(), c->Vacc.as<float>(), c->kp);
         }
     }));
@@ -1318,9 +1365,9 @@ int run_col_tail(plsa_ctx *c) {
         constexpr int GPB = 256 / Sh::LPN;
         const int grid2 = grid_for(c, c->m, GPB);
         Scope s(c, "k_col_reduce_norm");
-        hipLaunchKernelGGL((plsa::k_col_reduce_norm<Sh>), dim3(grid2 + c->n_heavy), dim3(256),
-                           sizeof(float) * (size_t)(GPB + 1) * c->kp, c->ls, c->item_first.as<int>(), (int)c->m,
-                           c->heavy_items, c->heavy_cols.as<int>(), c->n_heavy, c->partial.as<float>(),
+        hipLaunchKernelGGL((plsa::k_col_reduce_norm<Sh>), dim3(grid2 + c->csc.n_heavy), dim3(256),
+                           sizeof(float) * (size_t)(GPB + 1) * c->kp, c->ls, c->csc.item_first.as<int>(), (int)c->m,
+                           c->heavy_items, c->csc.heavy_cols.as<int>(), c->csc.n_heavy, c->partial.as<float>(),
                            c->norm_pwz.as<float>(), c->Vt[out_v(c)].as<float>(), c->kp);
     }));
     return launch_check(c, "k_col_reduce_norm");
@@ -1336,17 +1383,17 @@ int finish_ll(plsa_ctx *c, int blocks, double *out) {
     CHK(launch_check(c, "k_ll_final"));
     if (c->sharded && c->comm)      // log-likelihood of all shards: one scalar all-reduce per test
         NCCLCHK(c, ncclAllReduce(c->ll_out.p, c->ll_out.p, 1, ncclDouble, ncclSum, c->comm, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_ll, c->ll_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_ll.get(), c->ll_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (!out) return hipEventRecord(c->ev_ll, c->stream) == hipSuccess ? 0 : fail(c, "event record failed");   // collected by wait_ll
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *out = *c->h_ll;
+    *out = c->h_ll[0];
     return 0;
 }
 
 // second half of finish_ll(c, blocks, nullptr): the host waits for the likelihood only, not for the work enqueued behind it
 int wait_ll(plsa_ctx *c, double *out) {
     HIPCHK(c, hipEventSynchronize(c->ev_ll));
-    *out = *c->h_ll;
+    *out = c->h_ll[0];
     return 0;
 }
 
@@ -1368,7 +1415,7 @@ int run_loglik(plsa_ctx *c, const float *d_sw, double *out) {
 
 // one M-step from the materialised P: U[1-cu], and (update_v) Vt[1-cv]; swaps the buffers in
 int run_m_step_from_p(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz) {
-    if (!c->p_valid) return fail(c, "plsa_m_step: no P(z|w,d) on the device (run plsa_e_step or plsa_set_p)");
+    if (!c->p_state.valid) return fail(c, "plsa_m_step: no P(z|w,d) on the device (run plsa_e_step or plsa_set_p)");
     if (c->ref_sums) return run_ref_m_step(c, d_sw, update_v, d_norm_pdz);
     CHK(run_row_pass(c, true, false, nullptr, 0.f, d_norm_pdz, nullptr));
     if (update_v) {
@@ -1414,15 +1461,15 @@ int run_ref_e_step(plsa_ctx *c, float thresh) {
         auto go = [&](auto NZ) {
             constexpr int nz = decltype(NZ)::value;
             const i64 tiles = (c->nnz + 64 / nz - 1) / (64 / nz);
-            if (fuse && (rc_alloc = ensure(c, c->ref_tsum, sizeof(float) * (size_t)tiles * kp)) == 0) {
+            if (fuse && (rc_alloc = ensure(c, c->ref_tsum.sums, sizeof(float) * (size_t)tiles * kp)) == 0) {
                 hipLaunchKernelGGL((plsa::ref::k_ref_e_step_tiled<nz, true>), dim3(grid_for(c, tiles, 2)), dim3(128),
-                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, c->rowidx.as<int>(), c->col, c->nnz,
+                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, c->rowidx.ids.as<int>(), c->col, c->nnz,
                                    c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, c->val, c->ref_e_sw,
-                                   c->ref_tsum.as<float>());
-                c->ref_tsum_valid = true; c->ref_tsum_sw = c->ref_e_sw; c->ref_tsum_tj = 64 / nz;
+                                   c->ref_tsum.sums.as<float>());
+                c->ref_tsum.valid = true; c->ref_tsum.sw = c->ref_e_sw; c->ref_tsum.tj = 64 / nz;
             } else if (!rc_alloc) {
                 hipLaunchKernelGGL((plsa::ref::k_ref_e_step_tiled<nz, false>), dim3(grid_for(c, tiles, 2)), dim3(128),
-                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, c->rowidx.as<int>(), c->col, c->nnz,
+                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, c->rowidx.ids.as<int>(), c->col, c->nnz,
                                    c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, nullptr, nullptr, nullptr);
             }
         };
@@ -1436,11 +1483,11 @@ int run_ref_e_step(plsa_ctx *c, float thresh) {
     } else {
         Scope s(c, "k_ref_e_step");
         hipLaunchKernelGGL(plsa::ref::k_ref_e_step, dim3(grid_for(c, c->nnz, 256)), dim3(256), 0, c->stream,
-                           c->rowidx.as<int>(), c->col, c->nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
+                           c->rowidx.ids.as<int>(), c->col, c->nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
                            p_base(c), c->kp, thresh);
     }
     CHK(launch_check(c, "k_ref_e_step"));
-    c->p_valid = true;
+    c->p_state.valid = true;
     return 0;
 }
 
@@ -1448,22 +1495,22 @@ int run_ref_e_step(plsa_ctx *c, float thresh) {
 // walk (k_ref_pair_*), or by the serial chain (k_ref_norm_chain); same bits either way.
 // the reference arithmetic's long columns (PLSA_REF_HEAVY_MIN entries or more, default 2048; 0: none): list [count, columns...]
 int ensure_ref_heavy(plsa_ctx *c) {
-    if (c->ref_heavy_valid) return 0;
+    if (c->ref_heavy.valid) return 0;
     const char *e = getenv("PLSA_REF_HEAVY_MIN");
-    c->ref_heavy_min = e ? atoi(e) : 2048;
-    c->n_ref_heavy = 0;
-    if (c->ref_heavy_min > 0 && c->nnz > 0) {
-        CHK(ensure(c, c->ref_heavy, sizeof(int) * (size_t)(c->m + 1)));
-        HIPCHK(c, hipMemsetAsync(c->ref_heavy.p, 0, sizeof(int), c->stream));
+    c->ref_heavy.min = e ? atoi(e) : 2048;
+    c->ref_heavy.n = 0;
+    if (c->ref_heavy.min > 0 && c->nnz > 0) {
+        CHK(ensure(c, c->ref_heavy.cols, sizeof(int) * (size_t)(c->m + 1)));
+        HIPCHK(c, hipMemsetAsync(c->ref_heavy.cols.p, 0, sizeof(int), c->stream));
         hipLaunchKernelGGL(plsa::ref::k_ref_heavy_cols, dim3((unsigned)((c->m + 255) / 256)), dim3(256), 0, c->stream,
-                           c->colptr.as<int>(), (int)c->m, c->ref_heavy_min, c->ref_heavy.as<int>() + 1, c->ref_heavy.as<int>());
+                           c->csc.colptr.as<int>(), (int)c->m, c->ref_heavy.min, c->ref_heavy.cols.as<int>() + 1, c->ref_heavy.cols.as<int>());
         CHK(launch_check(c, "k_ref_heavy_cols"));
         int n = 0;
-        HIPCHK(c, hipMemcpyAsync(&n, c->ref_heavy.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&n, c->ref_heavy.cols.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->n_ref_heavy = n;
+        c->ref_heavy.n = n;
     }
-    c->ref_heavy_valid = true;
+    c->ref_heavy.valid = true;
     return 0;
 }
 
@@ -1471,7 +1518,7 @@ int ensure_ref_heavy(plsa_ctx *c) {
 // sums -> prefix -> (parity -> increment) pairs -> one checking walk per 64 topics), on c->ls.  kind / P / kp: PAIR_PLAIN or
 // PAIR_WEIGHTED over P(z|w,d) (norm_pwz, plsa.py:193), PAIR_NEG_TERMS over the likelihood terms with kp = 1 (plsa.py:322).
 int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const float *d_sw, float *out, unsigned long long *stats) {
-    const int *ri = c->rowidx.as<int>();
+    const int *ri = c->rowidx.ids.as<int>();
     const bool ll = kind == plsa::ref::PAIR_NEG_TERMS;              // (timing names: the likelihood's launches apart from norm_pwz's)
     // two levels (default): chunks of 256 addends, walked in groups of PAIR_R; PLSA_REF_LEVELS=1: chunks only, longer on large corpora
     bool two = true;
@@ -1504,12 +1551,12 @@ int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const floa
         constexpr int nz = decltype(NZ)::value;
         auto go = [&](auto KIND) {
             constexpr int kd = decltype(KIND)::value;
-            if (!ll && c->ref_tsum_valid && c->ref_tsum_sw == d_sw && P == p_base(c) && c->p_valid && L % c->ref_tsum_tj == 0) {
+            if (!ll && c->ref_tsum.valid && c->ref_tsum.sw == d_sw && P == p_base(c) && c->p_state.valid && L % c->ref_tsum.tj == 0) {
                 // the E-step that wrote this P left the sums of its tiles: no second pass over P
                 Scope s(c, "k_ref_pair_sums");
-                const i64 n_tiles = (c->nnz + c->ref_tsum_tj - 1) / c->ref_tsum_tj;
+                const i64 n_tiles = (c->nnz + c->ref_tsum.tj - 1) / c->ref_tsum.tj;
                 hipLaunchKernelGGL(plsa::ref::k_ref_pair_sums_from_tiles, dim3(grid_for(c, n_chunks * kp, 256)), dim3(256), 0, c->ls,
-                                   c->ref_tsum.as<float>(), kp, L / c->ref_tsum_tj, n_tiles, n_chunks, n_pad, csum);
+                                   c->ref_tsum.sums.as<float>(), kp, L / c->ref_tsum.tj, n_tiles, n_chunks, n_pad, csum);
             } else {
                 Scope s(c, ll ? "k_ref_ll_pair_sums" : "k_ref_pair_sums");
                 hipLaunchKernelGGL((plsa::ref::k_ref_pair_sums<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, c->val, c->nnz, P,
@@ -1557,7 +1604,7 @@ bool ref_pairs_now(const plsa_ctx *c) {
 
 int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw) {
     const int kp = c->kp;
-    const int *ri = c->rowidx.as<int>();
+    const int *ri = c->rowidx.ids.as<int>();
     float *out = c->norm_pwz.as<float>();
     if (c->nnz <= 0) { HIPCHK(c, hipMemsetAsync(out, 0, sizeof(float) * (size_t)kp, c->ls)); return 0; }
     // the last walk's count of slow chunks, if it has arrived (never waited for)
@@ -1590,15 +1637,15 @@ int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw) {
     }
     CHK(ensure(c, c->ref_stats, 32));
     if (!c->h_ref_stats) {
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_ref_stats), 16, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_ref_stats, hipEventDisableTiming));
+        HIPCHK(c, host_alloc(c->h_ref_stats, 2));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_ref_stats.h, hipEventDisableTiming));
     }
     unsigned long long *stats = c->ref_stats.as<unsigned long long>();
     HIPCHK(c, hipMemsetAsync(stats, 0, 16, c->ls));
     CHK(run_ref_pair_chain(c, d_sw ? plsa::ref::PAIR_WEIGHTED : plsa::ref::PAIR_PLAIN, p_base(c), kp, d_sw, out, stats));
     CHK(launch_check(c, "k_ref_pair_walk"));
     if (!c->ref_stats_pending) {       // (one read-back in flight at a time; a walk whose count is skipped is simply not counted)
-        HIPCHK(c, hipMemcpyAsync(c->h_ref_stats, stats, 16, hipMemcpyDeviceToHost, c->ls));
+        HIPCHK(c, hipMemcpyAsync(c->h_ref_stats.get(), stats, 16, hipMemcpyDeviceToHost, c->ls));
         HIPCHK(c, hipEventRecord(c->ev_ref_stats, c->ls));
         c->ref_stats_pending = true;
     }
@@ -1617,13 +1664,14 @@ int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_
         CHK(ensure_csc(c));
         CHK(ensure_rowidx(c));
         CHK(ensure_ref_heavy(c));
-        if (c->n_ref_heavy > 0) heavy_min = c->ref_heavy_min;
+        if (c->ref_heavy.n > 0) heavy_min = c->ref_heavy.min;
         CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        c->ls = c->stream2;
-        CHK(run_ref_norm_pwz(c, d_sw));
-        c->ls = c->stream;
+        {
+            LaunchOn on2(c, c->stream2);
+            CHK(run_ref_norm_pwz(c, d_sw));
+        }
         CHK(launch_check(c, "k_ref_norm_chain"));
         HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
     }
@@ -1648,11 +1696,11 @@ int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_
         if (update_v) {
             Scope s(c, "k_ref_col_pass");
             hipLaunchKernelGGL((plsa::ref::k_ref_col_pass<g, nz>), dim3(grid_for(c, c->m, 256 / g)), dim3(256), 0, c->stream,
-                               c->colptr.as<int>(), c->csc_row.as<int>(), c->csc_val.as<float>(), c->csc_pos.as<int>(),
+                               c->csc.colptr.as<int>(), c->csc.row.as<int>(), c->csc.val.as<float>(), c->csc.pos.as<int>(),
                                (int)c->m, p_base(c), d_sw, c->Vacc.as<float>(), c->kp, heavy_min);
         }
     }));
-    if (update_v && c->n_ref_heavy > 0) {
+    if (update_v && c->ref_heavy.n > 0) {
         // the long columns: one workgroup each, the norm_pwz chain's kernel over the column's entries (6.4 ns per entry where a
         // group's own walk costs ~160: the Zipf head was the pass -- 24.6 ms at the config-3 150 k sample, 157 ms at the whole)
         Scope s(c, "k_ref_col_heavy");
@@ -1660,13 +1708,13 @@ int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_
         auto go = [&](auto NZ) {
             constexpr int nz = decltype(NZ)::value;
             if (d_sw)
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, true, true>), dim3(c->n_ref_heavy), dim3(plsa::ref::CHAIN_THREADS), 0,
-                                   c->stream, c->csc_row.as<int>(), c->csc_val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(),
-                                   c->csc_pos.as<int>(), c->ref_heavy.as<int>() + 1, c->colptr.as<int>());
+                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, true, true>), dim3(c->ref_heavy.n), dim3(plsa::ref::CHAIN_THREADS), 0,
+                                   c->stream, c->csc.row.as<int>(), c->csc.val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(),
+                                   c->csc.pos.as<int>(), c->ref_heavy.cols.as<int>() + 1, c->csc.colptr.as<int>());
             else
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, false, true>), dim3(c->n_ref_heavy), dim3(plsa::ref::CHAIN_THREADS), 0,
-                                   c->stream, c->csc_row.as<int>(), c->csc_val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(),
-                                   c->csc_pos.as<int>(), c->ref_heavy.as<int>() + 1, c->colptr.as<int>());
+                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, false, true>), dim3(c->ref_heavy.n), dim3(plsa::ref::CHAIN_THREADS), 0,
+                                   c->stream, c->csc.row.as<int>(), c->csc.val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(),
+                                   c->csc.pos.as<int>(), c->ref_heavy.cols.as<int>() + 1, c->csc.colptr.as<int>());
         };
         using std::integral_constant;
         if (kp <= 64) go(integral_constant<int, 1>{});
@@ -1698,7 +1746,7 @@ int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out) {
     {
         Scope s(c, "k_ref_ll_terms");
         hipLaunchKernelGGL(plsa::ref::k_ref_ll_terms, dim3(grid_for(c, c->nnz, 256)), dim3(256), 0, c->stream,
-                           c->rowidx.as<int>(), c->col, c->val, c->nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
+                           c->rowidx.ids.as<int>(), c->col, c->val, c->nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
                            d_sw, c->kp, c->ref_terms.as<float>());
     }
     if (ref_pairs_now(c)) {
@@ -1714,9 +1762,9 @@ int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out) {
                            c->ll_out.as<double>());
     }
     CHK(launch_check(c, "k_ref_ll_chain"));
-    HIPCHK(c, hipMemcpyAsync(c->h_ll, c->ll_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_ll.get(), c->ll_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    *out = *c->h_ll;
+    *out = c->h_ll[0];
     return 0;
 }
 
@@ -1762,36 +1810,30 @@ int plsa_create(int device, plsa_ctx **out) {
     if (e != hipSuccess || cnt <= 0)
         return fail(nullptr, "no HIP device available (%s)", hipGetErrorString(e));
     if (device < 0 || device >= cnt) return fail(nullptr, "device %d out of range [0,%d)", device, cnt);
-    plsa_ctx *c = new plsa_ctx();
+    std::unique_ptr<plsa_ctx> owner(new plsa_ctx());      // (a failed creation frees whatever exists so far)
+    plsa_ctx *c = owner.get();
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&c->prop, device) != hipSuccess) {
-        delete c;
+    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&c->prop, device) != hipSuccess)
         return fail(nullptr, "hipSetDevice(%d) failed", device);
-    }
-    if (strncmp(c->prop.gcnArchName, "gfx950", 6) != 0) {
-        std::string arch = c->prop.gcnArchName;
-        delete c;
+    if (strncmp(c->prop.gcnArchName, "gfx950", 6) != 0)
         return fail(nullptr, "libplsa_hip is built for gfx950 (MI355X) only; device %d is %s", device,
-                    arch.c_str());
-    }
+                    c->prop.gcnArchName);
     // the second stream carries the short column tail underneath the document pass: highest priority, so that its
     // few workgroups are placed as soon as slots free up instead of queueing behind the pass' 32 k workgroups
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
     const char *prio_env = getenv("PLSA_TAIL_PRIORITY");
     const bool tail_prio = !prio_env || atoi(prio_env) != 0;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        (tail_prio ? hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_hi)
-                   : hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking)) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_row, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_ll, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_ll, sizeof(double) * 2, hipHostMallocDefault) != hipSuccess) {
-        delete c;
+    if (hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess ||
+        (tail_prio ? hipStreamCreateWithPriority(&c->stream2.h, hipStreamNonBlocking, prio_hi)
+                   : hipStreamCreateWithFlags(&c->stream2.h, hipStreamNonBlocking)) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_fork.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_join.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_row.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_tail.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_ll.h, hipEventDisableTiming) != hipSuccess ||
+        host_alloc(c->h_ll, 2) != hipSuccess)
         return fail(nullptr, "stream / pinned buffer creation failed");
-    }
     c->ls = c->stream;
     if (const char *s = getenv("PLSA_OVERLAP")) c->overlap = atoi(s) != 0;
     if (const char *s = getenv("PLSA_OVERLAP_FULL_LIMIT")) c->overlap_full_limit = atof(s);
@@ -1825,7 +1867,7 @@ int plsa_create(int device, plsa_ctx **out) {
     if (const char *s = getenv("PLSA_SPECULATE")) c->speculate = atoi(s);
     if (const char *s = getenv("PLSA_REF_CHAIN"))      // norm_pwz of the reference arithmetic: auto (default) | pairs | serial
         c->ref_chain_mode = !strcmp(s, "pairs") ? 1 : (!strcmp(s, "serial") ? 2 : 0);
-    *out = c;
+    *out = owner.release();
     return 0;
 }
 
@@ -1833,29 +1875,7 @@ void plsa_destroy(plsa_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->comm) { (void)ncclCommDestroy(c->comm); c->comm = nullptr; }
-    release(c->comm_send); release(c->comm_recv); release(c->comm_small); release(c->comm_stack);
-    if (c->comm_host) { (void)hipHostFree(c->comm_host); c->comm_host = nullptr; c->comm_host_cap = 0; }
-    release(c->item_end); release(c->colsum_rows); release(c->colsum_rows2);
-    release(c->item_rec); release(c->xcd_lo); release(c->t_end);
-    release(c->mt_words); release(c->mt_state); release(c->mt_fin); release(c->mt_poly); release(c->mt_seq);
-    DevBuf *all[] = {&c->b_indptr, &c->b_col, &c->b_val, &c->a_indptr, &c->a_col, &c->a_val, &c->rowidx,
-                     &c->colptr, &c->csc_row, &c->csc_val, &c->csc_pos, &c->item_first, &c->item_col,
-                     &c->item_start, &c->item_order, &c->partial, &c->heavy_cols, &c->row_order, &c->ritem_first, &c->ritem_row, &c->ritem_start, &c->rpartial, &c->eitem_row, &c->eitem_start, &c->U[0], &c->U[1], &c->U[2], &c->Vt[0], &c->Vt[1], &c->Vt[2], &c->Vacc,
-                     &c->P, &c->sw, &c->sw_res, &c->ll_partials, &c->ll_out, &c->colsum_partials, &c->norm_pwz,
-                     &c->norm_pdz, &c->tmp0, &c->tmp1, &c->tmp2, &c->cubtmp, &c->ref_terms, &c->ref_csum, &c->ref_pairs, &c->ref_exps, &c->ref_stats, &c->ref_ll_neg, &c->ref_heavy, &c->ref_pairs2, &c->ref_exps2, &c->ref_tsum};
-    if (c->p_borrowed) { c->P.p = nullptr; c->P.cap = 0; }      // lent memory is the lender's to free
-    for (DevBuf *b : all) release(*b);
-    for (auto &t : c->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-    for (auto e : c->pool) (void)hipEventDestroy(e);
-    if (c->h_ll) (void)hipHostFree(c->h_ll);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_row) (void)hipEventDestroy(c->ev_row);
-    if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-    if (c->ev_ll) (void)hipEventDestroy(c->ev_ll);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (c->comm) (void)ncclCommDestroy(c->comm);
     delete c;
 }
 
@@ -2006,7 +2026,7 @@ int plsa_set_factors(plsa_ctx *c, const float *U, const float *V, int64_t n, int
     for (int i = 0; i < 2; ++i) CHK(ensure(c, c->U[i], sizeof(float) * (size_t)n * kp));
     for (int i = 0; i < 2; ++i) CHK(ensure(c, c->Vt[i], sizeof(float) * (size_t)m * kp));
     CHK(ensure(c, c->Vacc, sizeof(float) * (size_t)m * kp));
-    c->p_valid = false;
+    c->p_state.invalidate();
     c->cu = 0;
     if (kp != k) HIPCHK(c, hipMemsetAsync(c->U[0].p, 0, sizeof(float) * (size_t)n * kp, c->stream));
     if (kp == k)
@@ -2039,7 +2059,7 @@ int plsa_init_factors_device(plsa_ctx *c, int32_t k, uint64_t seed) {
     for (int i = 0; i < 2; ++i) CHK(ensure(c, c->U[i], sizeof(float) * (size_t)n * kp));
     for (int i = 0; i < 2; ++i) CHK(ensure(c, c->Vt[i], sizeof(float) * (size_t)m * kp));
     CHK(ensure(c, c->Vacc, sizeof(float) * (size_t)m * kp));
-    c->p_valid = false; c->cu = 0; c->cv = 0;
+    c->p_state.invalidate(); c->cu = 0; c->cv = 0;
     // P(w|z): uniform draws per (topic, word), topic rows normalised -> generate [k, m] then transpose
     CHK(ensure(c, c->tmp0, sizeof(float) * (size_t)std::max<i64>(k, 4) * m));
     hipLaunchKernelGGL(plsa::k_init_rows, dim3(grid_for(c, k, 4)), dim3(256), 0, c->stream, c->tmp0.as<float>(),
@@ -2070,7 +2090,7 @@ static int mt_init(plsa_ctx *c, int32_t k, uint32_t *state_io /*[625]*/, const f
     for (int i = 0; i < 2; ++i) CHK(ensure(c, c->U[i], sizeof(float) * (size_t)n * kp));
     for (int i = 0; i < 2; ++i) CHK(ensure(c, c->Vt[i], sizeof(float) * (size_t)m * kp));
     CHK(ensure(c, c->Vacc, sizeof(float) * (size_t)m * kp));
-    c->p_valid = false; c->cu = 0; c->cv = 0;
+    c->p_state.invalidate(); c->cu = 0; c->cv = 0;
     const i64 v_doubles = V_host ? 0 : (i64)k * m;
     const i64 n_doubles = v_doubles + n * (i64)k;
     const i64 n_words = 2 * n_doubles;
@@ -2229,9 +2249,9 @@ int plsa_e_step(plsa_ctx *c, float thresh, float *P_out) {
 int plsa_set_p(plsa_ctx *c, const float *P) {
     HIPCHK(c, hipSetDevice(c->device));
     CHK(need_factors(c));
-    if (c->p_borrowed || c->p_lent) {
+    if (c->P.borrowed || c->p_lent) {
         if (c->P.cap < sizeof(float) * (size_t)(c->nnz + 64) * c->kp)
-            return fail(c, "plsa_set_p: the %s P(z|w,d) buffer is too small (it cannot be re-allocated while shared)", c->p_borrowed ? "borrowed" : "lent");
+            return fail(c, "plsa_set_p: the %s P(z|w,d) buffer is too small (it cannot be re-allocated while shared)", c->P.borrowed ? "borrowed" : "lent");
     } else
     CHK(ensure(c, c->P, sizeof(float) * (size_t)(c->nnz + 64) * c->kp + c->p_shift));
     if (c->kp != c->k) HIPCHK(c, hipMemsetAsync(p_base(c), 0, sizeof(float) * (size_t)c->nnz * c->kp, c->stream));
@@ -2239,8 +2259,8 @@ int plsa_set_p(plsa_ctx *c, const float *P) {
         HIPCHK(c, hipMemcpy2DAsync(p_base(c), sizeof(float) * c->kp, P, sizeof(float) * c->k,
                                    sizeof(float) * c->k, (size_t)c->nnz, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->p_valid = true;
-    c->ref_tsum_valid = false;
+    c->p_state.valid = true;
+    c->ref_tsum.invalidate();
     return 0;
 }
 
@@ -2394,7 +2414,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                 CHK(ensure_packed_csr(c));
                 CHK(ensure_ritems(c));
                 const int *unused = nullptr;
-                if (!c->use_ritems) CHK(ensure_roworder(c, &unused));
+                if (!c->ritems.use) CHK(ensure_roworder(c, &unused));
                 if (pipelined) {
                     // The column chain of successive iterations is one dependency chain (column pass -> tail -> next
                     // column pass): it stays back to back on the second stream, and the two streams only exchange
@@ -2402,11 +2422,11 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                     // put two cross-stream hops (17 us of 121 at config 1) between tail i and column pass i+1.
                     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail, 0));      // P(w|z) of the previous chain
                     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_row, 0));      // P(z|d) of the previous document pass
-                    c->ls = c->stream2;
-                    int rc = run_col_pass(c, false, d_sw_m, thresh, 1);
-                    if (!rc) rc = run_col_tail(c);
-                    c->ls = c->stream;
-                    if (rc) return rc;
+                    {
+                        LaunchOn on2(c, c->stream2);
+                        CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
+                        CHK(run_col_tail(c));
+                    }
                     HIPCHK(c, hipEventRecord(c->ev_tail, c->stream2));
                     CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
                     HIPCHK(c, hipEventRecord(c->ev_row, c->stream));
@@ -2414,11 +2434,11 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                 }
                 HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
                 HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-                c->ls = c->stream2;
-                int rc = run_col_pass(c, false, d_sw_m, thresh, 1);
-                if (!rc) rc = run_col_tail(c);
-                c->ls = c->stream;
-                if (rc) return rc;
+                {
+                    LaunchOn on2(c, c->stream2);
+                    CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
+                    CHK(run_col_tail(c));
+                }
                 HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
                 CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
@@ -2430,10 +2450,10 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                 CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
                 HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
                 HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-                c->ls = c->stream2;
-                int rc = run_col_tail(c);
-                c->ls = c->stream;
-                if (rc) return rc;
+                {
+                    LaunchOn on2(c, c->stream2);
+                    CHK(run_col_tail(c));
+                }
                 HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
                 CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
@@ -2654,7 +2674,7 @@ int plsa_em_accumulate_materialised(plsa_ctx *c, const float *sw, float thresh, 
     // P(z|w,d) may be another context's by the next call (plsa_p_borrow): its last reader has finished when this returns
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream2));
-    c->p_valid = false;
+    c->p_state.invalidate();
     return 0;
 }
 
@@ -2662,7 +2682,7 @@ int plsa_em_accumulate_materialised(plsa_ctx *c, const float *sw, float thresh, 
 int plsa_p_reserve(plsa_ctx *c, int64_t bytes, void **device_ptr) {
     HIPCHK(c, hipSetDevice(c->device));
     if (bytes <= 0 || !device_ptr) return fail(c, "plsa_p_reserve: bad arguments");
-    if (c->p_borrowed) return fail(c, "plsa_p_reserve: this context borrows its P(z|w,d) buffer");
+    if (c->P.borrowed) return fail(c, "plsa_p_reserve: this context borrows its P(z|w,d) buffer");
     if (c->p_lent && c->P.cap < (size_t)bytes)
         return fail(c, "plsa_p_reserve: the buffer handed out earlier (%.2f GB) cannot grow to %.2f GB while other contexts may hold its "
                        "address: end the loans (plsa_p_borrow(NULL)) and call plsa_release_scratch first", c->P.cap / 1e9, bytes / 1e9);
@@ -2670,7 +2690,7 @@ int plsa_p_reserve(plsa_ctx *c, int64_t bytes, void **device_ptr) {
     CHK(ensure(c, c->P, (size_t)bytes));
     c->p_lent = true;
     c->p_shift = 0;
-    c->p_valid = false;
+    c->p_state.invalidate();
     *device_ptr = c->P.p;
     return 0;
 }
@@ -2681,11 +2701,8 @@ int plsa_p_reserve(plsa_ctx *c, int64_t bytes, void **device_ptr) {
 int plsa_p_borrow(plsa_ctx *c, void *device_ptr, int64_t bytes) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!c->p_borrowed) release(c->P);
-    c->P.p = device_ptr;
-    c->P.cap = device_ptr ? (size_t)std::max<int64_t>(bytes, 0) : 0;
-    c->p_borrowed = device_ptr != nullptr;
-    c->p_valid = false;
+    c->P.borrow(device_ptr, (size_t)std::max<int64_t>(bytes, 0));
+    c->p_state.invalidate();
     c->p_shift = 0;
     return 0;
 }
@@ -2820,8 +2837,8 @@ static int allgather_stack_impl(plsa_ctx *c, int64_t slots, int64_t m, int32_t k
         return fail(c, "plsa_comm_allgather_stack: no stack of %lld slots reserved (plsa_stack_reserve)", (long long)slots);
     const size_t bytes = sizeof(float) * (size_t)slots * km * world;
     if (!dst && c->comm_host_cap < bytes) {
-        if (c->comm_host) { HIPCHK(c, hipHostFree(c->comm_host)); c->comm_host = nullptr; c->comm_host_cap = 0; }
-        HIPCHK(c, hipHostMalloc((void **)&c->comm_host, bytes, hipHostMallocDefault));
+        c->comm_host_cap = 0;
+        HIPCHK(c, host_alloc(c->comm_host, bytes / sizeof(float)));
         c->comm_host_cap = bytes;
     }
     const float *src = c->comm_stack.as<float>();
@@ -2835,7 +2852,7 @@ static int allgather_stack_impl(plsa_ctx *c, int64_t slots, int64_t m, int32_t k
         NCCLCHK(c, ncclGroupEnd());
         src = c->comm_recv.as<float>();
     }
-    float *to = dst ? dst : c->comm_host;
+    float *to = dst ? dst : c->comm_host.get();
     HIPCHK(c, hipMemcpyAsync(to, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (host_view) *host_view = to;
@@ -2924,17 +2941,17 @@ int plsa_placement_info(plsa_ctx *c, int32_t *candidates, double *best_gbps, dou
 
 int plsa_schedule_info(plsa_ctx *c, int32_t *xcd_lo, double *xcd_end_us, int32_t *timed_launches, int32_t *item_len,
                        int64_t *n_items) {
-    if (xcd_lo) for (int x = 0; x <= 8; ++x) xcd_lo[x] = c->bal_valid ? c->bal_lo[x] : 0;
+    if (xcd_lo) for (int x = 0; x <= 8; ++x) xcd_lo[x] = c->csc.balanced ? c->bal_lo[x] : 0;
     if (xcd_end_us) for (int x = 0; x < 8; ++x) xcd_end_us[x] = c->bal_launches > 0 ? c->bal_end_us[x] : 0.0;
     if (timed_launches) *timed_launches = c->bal_launches;
-    if (item_len) *item_len = c->csc_valid ? c->seg : 0;
-    if (n_items) *n_items = c->csc_valid ? c->n_items : 0;
+    if (item_len) *item_len = c->csc.valid ? c->csc.seg : 0;
+    if (n_items) *n_items = c->csc.valid ? c->csc.n_items : 0;
     return 0;
 }
 
 int plsa_packed_info(plsa_ctx *c, int32_t *csr, int32_t *csc) {
-    if (csr) *csr = !c->packed ? 0 : (c->pk_csr_valid ? (c->pk_csr_ok ? 1 : 0) : -1);
-    if (csc) *csc = !c->packed ? 0 : (c->csc_valid && c->pk_csc_valid ? (c->pk_csc_ok ? 1 : 0) : -1);
+    if (csr) *csr = !c->packed ? 0 : (c->pk_csr.valid ? (c->pk_csr.ok ? 1 : 0) : -1);
+    if (csc) *csc = !c->packed ? 0 : (c->csc.valid && c->pk_csc.valid ? (c->pk_csc.ok ? 1 : 0) : -1);
     return 0;
 }
 
@@ -2943,23 +2960,23 @@ int plsa_release_scratch(plsa_ctx *c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // a BORROWED P(z|w,d) stays borrowed (nothing of this context's own would be freed, and silently dropping the loan made
     // the next materialising call allocate a private full-size array); a LENT one is freed: the caller ends the loans first
-    if (!c->p_borrowed) release(c->P);
+    c->P.release();
     c->p_lent = false;
-    release(c->ref_terms); release(c->ref_csum); release(c->ref_pairs); release(c->ref_exps); release(c->ref_ll_neg); release(c->ref_heavy); release(c->ref_pairs2); release(c->ref_exps2); release(c->ref_tsum);
-    release(c->partial); release(c->tmp0); release(c->tmp1); release(c->tmp2); release(c->cubtmp);
-    // packed entry streams (rebuilt by the next fused pass; the CSC arrays they are packed from stay)
-    release(c->pk_csr); release(c->pk_csc); release(c->pk_count);
-    c->pk_csr_valid = c->pk_csc_valid = false;
-    c->pk_csr_ok = c->pk_csc_ok = false;
-    release(c->mt_words); release(c->mt_state); release(c->mt_fin); release(c->mt_poly); release(c->mt_seq);
-    // member stack + gather buffers of the ensemble exchange (16 runs x 64 topics x 100 k words = 0.4 GB): re-created
-    // by the next plsa_stack_reserve / plsa_comm_allgather_stack
+    c->p_state.drop();
+    c->p_shift = 0;
+    // derived structures kept only for the reference arithmetic / the fused passes: rebuilt on demand (the packed entry
+    // streams by the next fused pass, from the CSC arrays, which stay)
+    c->ref_heavy.drop(); c->ref_tsum.drop(); c->pk_csr.drop(); c->pk_csc.drop();
+    for (DevBuf *b : {&c->ref_terms, &c->ref_csum, &c->ref_pairs, &c->ref_exps, &c->ref_ll_neg, &c->ref_pairs2, &c->ref_exps2,
+                      &c->partial, &c->tmp0, &c->tmp1, &c->tmp2, &c->cubtmp, &c->pk_count,
+                      &c->mt_words, &c->mt_state, &c->mt_fin, &c->mt_poly, &c->mt_seq,
+                      // member stack + gather buffers of the ensemble exchange (16 runs x 64 topics x 100 k words = 0.4 GB):
+                      // re-created by the next plsa_stack_reserve / plsa_comm_allgather_stack
+                      &c->comm_stack, &c->comm_recv, &c->comm_send})
+        b->release();
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
     // gather that needs a larger one, or plsa_destroy.
-    release(c->comm_stack); release(c->comm_recv); release(c->comm_send);
-    c->p_valid = false;
-    c->p_shift = 0;
     return 0;
 }
 
@@ -3006,11 +3023,10 @@ int plsa_measure_stream_bandwidth(plsa_ctx *c, int64_t bytes, int32_t kind, int3
     if (bytes < (1 << 20) || reps < 1 || kind < 0 || kind > 6) return fail(c, "plsa_measure_stream_bandwidth: bad arguments");
     DevBuf a, b;
     const i64 n4 = bytes / 16;
-    int rc = ensure(c, a, (size_t)n4 * 16);
-    if (!rc && kind == 2) rc = ensure(c, b, (size_t)n4 * 16);
-    if (rc) { release(a); release(b); return rc; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    CHK(ensure(c, a, (size_t)n4 * 16));
+    if (kind == 2) CHK(ensure(c, b, (size_t)n4 * 16));
+    Event e0, e1;
+    (void)hipEventCreate(&e0.h); (void)hipEventCreate(&e1.h);
     const int grid = grid_for(c, n4, 256);
     for (int r = -1; r < reps; ++r) {          // r == -1: untimed warm-up (page faults, clocks)
         if (r == 0) (void)hipEventRecord(e0, c->stream);
@@ -3024,8 +3040,6 @@ int plsa_measure_stream_bandwidth(plsa_ctx *c, int64_t bytes, int32_t kind, int3
     hipError_t e = hipStreamSynchronize(c->stream);
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    release(a); release(b);
     if (e != hipSuccess) return fail(c, "stream probe failed: %s", hipGetErrorString(e));
     const double moved = (double)n4 * 16.0 * (kind == 2 ? 2.0 : 1.0) * reps;
     *gbps = moved / 1e9 / (ms / 1e3);
@@ -3056,30 +3070,25 @@ int plsa_all_pairs_hellinger(plsa_ctx *c, const float *topics, int64_t t, int64_
     i64 slice = ((m + slices - 1) / slices + plsa::HELL_KSTEP - 1) / plsa::HELL_KSTEP * plsa::HELL_KSTEP;
     slices = (int)((m + slice - 1) / slice);
     DevBuf R, l1, part, dD, dt;
-    int rc = ensure(c, R, sizeof(float) * (size_t)t * m);
-    if (!rc) rc = ensure(c, l1, sizeof(double) * (size_t)t);
-    if (!rc) rc = ensure(c, part, sizeof(double) * (size_t)slices * t * t);
-    if (!rc) rc = ensure(c, dD, sizeof(double) * (size_t)t * t);
-    if (!rc) rc = ensure(c, dt, sizeof(int) * 2 * ti.size());
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(R.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dt.p, ti.data(), sizeof(int) * ti.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dt.as<int>() + ti.size(), tj.data(), sizeof(int) * tj.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(plsa::k_hell_prepare, dim3((unsigned)t), dim3(256), 0, c->stream, R.as<float>(), (int)t, (i64)m, l1.as<double>());
-            { Scope s(c, "k_hell_gram");
-              hipLaunchKernelGGL(plsa::k_hell_gram, dim3((unsigned)ti.size(), (unsigned)slices), dim3(256), 0, c->stream,
-                                 R.as<float>(), (int)t, (i64)m, slice, dt.as<int>(), dt.as<int>() + ti.size(), part.as<double>()); }
-            hipLaunchKernelGGL(plsa::k_hell_finish, dim3((unsigned)((t * t + 255) / 256)), dim3(256), 0, c->stream,
-                               part.as<double>(), slices, (int)t, l1.as<double>(), dD.as<double>());
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    CHK(ensure(c, R, sizeof(float) * (size_t)t * m));
+    CHK(ensure(c, l1, sizeof(double) * (size_t)t));
+    CHK(ensure(c, part, sizeof(double) * (size_t)slices * t * t));
+    CHK(ensure(c, dD, sizeof(double) * (size_t)t * t));
+    CHK(ensure(c, dt, sizeof(int) * 2 * ti.size()));
+    hipError_t e = hipMemcpyAsync(R.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dt.p, ti.data(), sizeof(int) * ti.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dt.as<int>() + ti.size(), tj.data(), sizeof(int) * tj.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(plsa::k_hell_prepare, dim3((unsigned)t), dim3(256), 0, c->stream, R.as<float>(), (int)t, (i64)m, l1.as<double>());
+        { Scope s(c, "k_hell_gram");
+          hipLaunchKernelGGL(plsa::k_hell_gram, dim3((unsigned)ti.size(), (unsigned)slices), dim3(256), 0, c->stream,
+                             R.as<float>(), (int)t, (i64)m, slice, dt.as<int>(), dt.as<int>() + ti.size(), part.as<double>()); }
+        hipLaunchKernelGGL(plsa::k_hell_finish, dim3((unsigned)((t * t + 255) / 256)), dim3(256), 0, c->stream,
+                           part.as<double>(), slices, (int)t, l1.as<double>(), dD.as<double>());
+        e = hipGetLastError();
     }
-    release(R); release(l1); release(part); release(dD); release(dt);
-    if (rc) return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, "plsa_all_pairs_hellinger: %s", hipGetErrorString(e));
     return 0;
 }
@@ -3095,25 +3104,20 @@ int plsa_all_pairs_kl(plsa_ctx *c, const float *topics, int64_t t, int64_t m, do
     i64 slice = ((m + slices - 1) / slices + plsa::HELL_KSTEP - 1) / plsa::HELL_KSTEP * plsa::HELL_KSTEP;
     slices = (int)((m + slice - 1) / slice);
     DevBuf T, part, dD;
-    int rc = ensure(c, T, sizeof(float) * (size_t)t * m);
-    if (!rc) rc = ensure(c, part, sizeof(double) * (size_t)slices * t * t);
-    if (!rc) rc = ensure(c, dD, sizeof(double) * (size_t)t * t);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(T.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            { Scope s(c, "k_kl_gram");
-              hipLaunchKernelGGL(plsa::k_kl_gram, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, c->stream,
-                                 T.as<float>(), (int)t, (i64)m, slice, part.as<double>()); }
-            hipLaunchKernelGGL(plsa::k_sum_slices, dim3((unsigned)((t * t + 255) / 256)), dim3(256), 0, c->stream,
-                               part.as<double>(), slices, (i64)t * t, dD.as<double>());
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    CHK(ensure(c, T, sizeof(float) * (size_t)t * m));
+    CHK(ensure(c, part, sizeof(double) * (size_t)slices * t * t));
+    CHK(ensure(c, dD, sizeof(double) * (size_t)t * t));
+    hipError_t e = hipMemcpyAsync(T.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        { Scope s(c, "k_kl_gram");
+          hipLaunchKernelGGL(plsa::k_kl_gram, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, c->stream,
+                             T.as<float>(), (int)t, (i64)m, slice, part.as<double>()); }
+        hipLaunchKernelGGL(plsa::k_sum_slices, dim3((unsigned)((t * t + 255) / 256)), dim3(256), 0, c->stream,
+                           part.as<double>(), slices, (i64)t * t, dD.as<double>());
+        e = hipGetLastError();
     }
-    release(T); release(part); release(dD);
-    if (rc) return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, "plsa_all_pairs_kl: %s", hipGetErrorString(e));
     return 0;
 }
@@ -3140,32 +3144,27 @@ int plsa_cluster_representatives(plsa_ctx *c, const float *topics, int64_t t, in
     // enstop_.py:385-393 np.average raises on an all-zero weight vector; callers handle that case
     const int nb = (int)((m + 255) / 256);
     DevBuf T, dfirst, dmem, dw, rep, bs, dout;
-    int rc = ensure(c, T, sizeof(float) * (size_t)t * m);
-    if (!rc) rc = ensure(c, dfirst, sizeof(int) * first.size());
-    if (!rc) rc = ensure(c, dmem, sizeof(int) * members.size());
-    if (!rc && weights) rc = ensure(c, dw, sizeof(double) * (size_t)t);
-    if (!rc) rc = ensure(c, rep, sizeof(double) * (size_t)n_clusters * m);
-    if (!rc) rc = ensure(c, bs, sizeof(double) * (size_t)n_clusters * nb);
-    if (!rc) rc = ensure(c, dout, sizeof(float) * (size_t)n_clusters * m);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(T.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dfirst.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dmem.p, members.data(), sizeof(int) * members.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && weights) e = hipMemcpyAsync(dw.p, weights, sizeof(double) * (size_t)t, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(plsa::k_rep_accumulate, dim3((unsigned)nb, (unsigned)n_clusters), dim3(256), 0, c->stream,
-                               T.as<float>(), (i64)m, dfirst.as<int>(), dmem.as<int>(), weights ? dw.as<double>() : nullptr,
-                               rep.as<double>(), bs.as<double>());
-            hipLaunchKernelGGL(plsa::k_rep_normalise, dim3((unsigned)nb, (unsigned)n_clusters), dim3(256), 0, c->stream,
-                               rep.as<double>(), (i64)m, bs.as<double>(), nb, dout.as<float>());
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n_clusters * m, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    CHK(ensure(c, T, sizeof(float) * (size_t)t * m));
+    CHK(ensure(c, dfirst, sizeof(int) * first.size()));
+    CHK(ensure(c, dmem, sizeof(int) * members.size()));
+    if (weights) CHK(ensure(c, dw, sizeof(double) * (size_t)t));
+    CHK(ensure(c, rep, sizeof(double) * (size_t)n_clusters * m));
+    CHK(ensure(c, bs, sizeof(double) * (size_t)n_clusters * nb));
+    CHK(ensure(c, dout, sizeof(float) * (size_t)n_clusters * m));
+    hipError_t e = hipMemcpyAsync(T.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dfirst.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dmem.p, members.data(), sizeof(int) * members.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && weights) e = hipMemcpyAsync(dw.p, weights, sizeof(double) * (size_t)t, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(plsa::k_rep_accumulate, dim3((unsigned)nb, (unsigned)n_clusters), dim3(256), 0, c->stream,
+                           T.as<float>(), (i64)m, dfirst.as<int>(), dmem.as<int>(), weights ? dw.as<double>() : nullptr,
+                           rep.as<double>(), bs.as<double>());
+        hipLaunchKernelGGL(plsa::k_rep_normalise, dim3((unsigned)nb, (unsigned)n_clusters), dim3(256), 0, c->stream,
+                           rep.as<double>(), (i64)m, bs.as<double>(), nb, dout.as<float>());
+        e = hipGetLastError();
     }
-    release(T); release(dfirst); release(dmem); release(dw); release(rep); release(bs); release(dout);
-    if (rc) return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n_clusters * m, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, "plsa_cluster_representatives: %s", hipGetErrorString(e));
     return 0;
 }
@@ -3212,17 +3211,13 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
         perm[2 * (size_t)k0] = a; perm[2 * (size_t)k0 + 1] = b;
     }
     DevBuf d_cdf, d_tok, d_ptr, d_keys, d_keys2, d_flag, d_pos, d_perm;
-    auto cleanup = [&]() { release(d_cdf); release(d_tok); release(d_ptr); release(d_keys);
-                           release(d_keys2); release(d_flag); release(d_pos); release(d_perm); };
-#define SYN(expr) do { int r_ = (expr); if (r_) { cleanup(); return r_; } } while (0)
-#define SYNHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); \
-        return fail(c, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    SYN(ensure(c, d_cdf, sizeof(double) * (size_t)m));
+#define SYNHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(c, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+    CHK(ensure(c, d_cdf, sizeof(double) * (size_t)m));
     SYNHIP(hipMemcpyAsync(d_cdf.p, cdf.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    SYN(ensure(c, d_tok, sizeof(int) * (size_t)(n + 1)));
-    SYN(ensure(c, d_ptr, sizeof(i64) * (size_t)(n + 1)));
+    CHK(ensure(c, d_tok, sizeof(int) * (size_t)(n + 1)));
+    CHK(ensure(c, d_ptr, sizeof(i64) * (size_t)(n + 1)));
     if (k0 > 0) {
-        SYN(ensure(c, d_perm, sizeof(uint64_t) * perm.size()));
+        CHK(ensure(c, d_perm, sizeof(uint64_t) * perm.size()));
         SYNHIP(hipMemcpyAsync(d_perm.p, perm.data(), sizeof(uint64_t) * perm.size(), hipMemcpyHostToDevice, c->stream));
     }
     const double sigma = 0.6;
@@ -3239,16 +3234,16 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
             auto in64 = hipcub::TransformInputIterator<i64, hipcub::CastOp<i64>, int *>(d_tok.as<int>(), hipcub::CastOp<i64>());
             size_t bytes = 0;
             SYNHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in64, d_ptr.as<i64>(), (int)(n + 1), c->stream));
-            SYN(ensure(c, c->cubtmp, bytes));
+            CHK(ensure(c, c->cubtmp, bytes));
             SYNHIP(hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, bytes, in64, d_ptr.as<i64>(), (int)(n + 1), c->stream));
         }
         SYNHIP(hipMemcpyAsync(&T, d_ptr.as<i64>() + n, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
         SYNHIP(hipStreamSynchronize(c->stream));
-        if (T >= INT32_MAX) { cleanup(); return fail(c, "plsa_generate_synthetic: %lld tokens >= 2^31", (long long)T); }
-        SYN(ensure(c, d_keys, sizeof(unsigned long long) * (size_t)T));
-        SYN(ensure(c, d_keys2, sizeof(unsigned long long) * (size_t)T));
-        SYN(ensure(c, d_flag, sizeof(int) * (size_t)T));
-        SYN(ensure(c, d_pos, sizeof(int) * (size_t)T));
+        if (T >= INT32_MAX) return fail(c, "plsa_generate_synthetic: %lld tokens >= 2^31", (long long)T);
+        CHK(ensure(c, d_keys, sizeof(unsigned long long) * (size_t)T));
+        CHK(ensure(c, d_keys2, sizeof(unsigned long long) * (size_t)T));
+        CHK(ensure(c, d_flag, sizeof(int) * (size_t)T));
+        CHK(ensure(c, d_pos, sizeof(int) * (size_t)T));
         if (k0 > 0)
             hipLaunchKernelGGL(plsa::k_synth_draw_topics, dim3(grid_for(c, n, 4)), dim3(256), 0, c->stream, (int)n, (int)m,
                                d_ptr.as<i64>(), d_cdf.as<double>(), d_perm.as<uint64_t>(), k0, alpha, background, seed,
@@ -3260,7 +3255,7 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
             size_t bytes = 0;
             SYNHIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, d_keys.as<unsigned long long>(),
                                                      d_keys2.as<unsigned long long>(), T, 0, 32 + dbits, c->stream));
-            SYN(ensure(c, c->cubtmp, bytes));
+            CHK(ensure(c, c->cubtmp, bytes));
             SYNHIP(hipcub::DeviceRadixSort::SortKeys(c->cubtmp.p, bytes, d_keys.as<unsigned long long>(),
                                                      d_keys2.as<unsigned long long>(), T, 0, 32 + dbits, c->stream));
         }
@@ -3269,7 +3264,7 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
         {
             size_t bytes = 0;
             SYNHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_flag.as<int>(), d_pos.as<int>(), (int)T, c->stream));
-            SYN(ensure(c, c->cubtmp, bytes));
+            CHK(ensure(c, c->cubtmp, bytes));
             SYNHIP(hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, bytes, d_flag.as<int>(), d_pos.as<int>(), (int)T, c->stream));
         }
         int last_pos = 0, last_flag = 0;
@@ -3282,17 +3277,15 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
         // distinct pairs grow sub-linearly in tokens: damped multiplicative correction
         mean_tokens *= std::pow((double)nnz_target / (double)nnz, 1.25);
     }
-    SYN(ensure(c, c->b_indptr, sizeof(int) * (size_t)(n + 1)));
-    SYN(ensure(c, c->b_col, sizeof(int) * (size_t)nnz));
-    SYN(ensure(c, c->b_val, sizeof(float) * (size_t)nnz));
+    CHK(ensure(c, c->b_indptr, sizeof(int) * (size_t)(n + 1)));
+    CHK(ensure(c, c->b_col, sizeof(int) * (size_t)nnz));
+    CHK(ensure(c, c->b_val, sizeof(float) * (size_t)nnz));
     hipLaunchKernelGGL(plsa::k_synth_emit, dim3(grid_for(c, T, 256)), dim3(256), 0, c->stream,
                        d_keys2.as<unsigned long long>(), T, d_flag.as<int>(), d_pos.as<int>(), (int)n, nnz,
                        c->b_indptr.as<int>(), c->b_col.as<int>(), c->b_val.as<float>());
-    SYN(launch_check(c, "k_synth_emit"));
+    CHK(launch_check(c, "k_synth_emit"));
     SYNHIP(hipStreamSynchronize(c->stream));
-#undef SYN
 #undef SYNHIP
-    cleanup();
     c->bn = n; c->bm = m; c->bnnz = nnz;
     c->active_is_base = true;
     set_active_pointers(c);

@@ -434,7 +434,7 @@ def test_long_columns_through_the_chain_kernel(amd, k, monkeypatch):
     """plsa.py:190 / :296: the vocabulary half of the M-step with the long columns handed to k_ref_norm_chain<GATHER> (one
     workgroup per column, the entries' rows of P found through their COO positions) -- here from 16 entries on, so that most
     columns of a small corpus go that way, one of them holding every document: Vacc, and with it P(w|z), bit for bit the oracle's,
-    with and without sample weights."""
+    with and without sample weights -- and again on the same upload after release_scratch, which frees the long-column list."""
     import scipy.sparse as sp
     from oracle.plsa_oracle import Oracle
     monkeypatch.setenv("PLSA_REF_HEAVY_MIN", "16")
@@ -452,18 +452,21 @@ def test_long_columns_through_the_chain_kernel(amd, k, monkeypatch):
     with amd.Engine() as eng:
         eng.upload_csr(X)
         eng.set_arithmetic("reference")
-        for weights in (None, sw):
-            Vo, Uo = V0.copy(), U0.copy()
-            nw_o, nd_o = np.zeros(k, np.float32), np.zeros(n, np.float32)
-            if weights is None:
-                o.plsa_m_step(r, c, v, Vo, Uo, P, nw_o, nd_o)
-            else:
-                o.plsa_m_step_w_sample_weight(r, c, v, Vo, Uo, P, weights, nw_o, nd_o)
-            eng.set_factors(U0, V0)
-            eng.set_p(P)
-            nw, nd = eng.m_step(weights)
-            U, V = eng.get_factors()
-            same_bits(nw, nw_o, "norm_pwz"); same_bits(V, Vo, "P(w|z)"); same_bits(U, Uo, "P(z|d)")
+        for released in (False, True):
+            if released:
+                eng.release_scratch()
+            for weights in (None, sw):
+                Vo, Uo = V0.copy(), U0.copy()
+                nw_o, nd_o = np.zeros(k, np.float32), np.zeros(n, np.float32)
+                if weights is None:
+                    o.plsa_m_step(r, c, v, Vo, Uo, P, nw_o, nd_o)
+                else:
+                    o.plsa_m_step_w_sample_weight(r, c, v, Vo, Uo, P, weights, nw_o, nd_o)
+                eng.set_factors(U0, V0)
+                eng.set_p(P)
+                nw, nd = eng.m_step(weights)
+                U, V = eng.get_factors()
+                same_bits(nw, nw_o, "norm_pwz"); same_bits(V, Vo, "P(w|z)"); same_bits(U, Uo, "P(z|d)")
 
 
 @pytest.mark.parametrize("k", [5, 64, 130])
