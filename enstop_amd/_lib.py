@@ -86,6 +86,7 @@ SIGNATURES = {
     "plsa_schedule_info": (C.c_int, [_ctx, C.POINTER(_i32), C.POINTER(C.c_double), C.POINTER(_i32), C.POINTER(_i32),
                                      C.POINTER(C.c_int64)]),
     "plsa_packed_info": (C.c_int, [_ctx, C.POINTER(_i32), C.POINTER(_i32)]),
+    "plsa_pass_info": (C.c_int, [_ctx, _i32p, _i32p, _i32p]),
     "plsa_release_scratch": (C.c_int, [_ctx]),
     "plsa_timing_enable": (C.c_int, [_ctx, _i32]),
     "plsa_timing_reset": (C.c_int, [_ctx]),

@@ -2955,6 +2955,15 @@ int plsa_packed_info(plsa_ctx *c, int32_t *csr, int32_t *csc) {
     return 0;
 }
 
+int plsa_pass_info(plsa_ctx *c, int32_t *col, int32_t *row, int32_t *wide) {
+    if (c->k <= 0) return fail(c, "plsa_pass_info: factors not set (call plsa_set_factors)");
+    if (col) { col[0] = c->lpn; col[1] = c->ch; col[2] = c->kp == 4 * c->lpn * c->ch; }
+    if (row) { row[0] = c->row_lpn; row[1] = c->row_ch; row[2] = c->kp == 4 * c->row_lpn * c->row_ch; }
+    // the tables each fused pass gathers from (dispatch_shape_row, run_col_pass): P(w|z), m rows; P(z|d), n rows
+    if (wide) { wide[0] = table_is_wide(c, c->m); wide[1] = table_is_wide(c, c->n); }
+    return 0;
+}
+
 int plsa_release_scratch(plsa_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -69,6 +69,13 @@ __device__ __forceinline__ float group_sum(float v) {
 }
 
 __device__ __forceinline__ float hsum(const float4 &a) { return (a.x + a.y) + (a.z + a.w); }
+// the same sum of four ROUNDED products (the log-likelihood's P(w|d), plsa.py:381) with contraction off: otherwise each
+// instantiation may fuse a different one of the multiplies into the adds, and the narrow and the WIDE form of one lane shape
+// (k <= 4: Shape<1, 1, true, false> / <1, 1, false, true>) gave log-likelihoods that differ in their last bits
+__device__ __forceinline__ float hsum_products(const float4 &a) {
+#pragma clang fp contract(off)
+    return (a.x + a.y) + (a.z + a.w);
+}
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -183,7 +190,7 @@ __device__ __forceinline__ float products(const float4 (&u)[CH], const float4 (&
     for (int j = 0; j < CH; ++j) {
         float4 v;
         v.x = vt[j].x * u[j].x; v.y = vt[j].y * u[j].y; v.z = vt[j].z * u[j].z; v.w = vt[j].w * u[j].w;
-        if (WANT_UNTH) unth = j ? unth + hsum(v) : hsum(v);
+        if (WANT_UNTH) unth = j ? unth + hsum_products(v) : hsum_products(v);
         keep[j].x = v.x > thresh ? v.x : 0.f;
         keep[j].y = v.y > thresh ? v.y : 0.f;
         keep[j].z = v.z > thresh ? v.z : 0.f;

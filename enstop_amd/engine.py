@@ -465,6 +465,15 @@ class Engine:
         name = {1: "packed", 0: "arrays", -1: None}
         return dict(csr=name[a.value], csc=name[b.value])
 
+    def pass_info(self):
+        """Instantiation each fused pass takes for the factors in force: lane shape (lpn, ch, full) of the column pass
+        (the E-step and the log-likelihood share it) and of the document pass, and whether each gathers with 64-bit
+        row addresses (a wide pass runs the run-time-kp instantiation whatever `full` says)."""
+        col, row, wide = np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(2, np.int32)
+        self._ok(self._L.plsa_pass_info(self._h, col, row, wide))
+        return dict(col=(int(col[0]), int(col[1]), bool(col[2])), row=(int(row[0]), int(row[1]), bool(row[2])),
+                    row_wide=bool(wide[0]), col_wide=bool(wide[1]))
+
     def release_scratch(self):
         """Free the materialised P and other large scratch buffers (re-created on demand)."""
         self._ok(self._L.plsa_release_scratch(self._h))

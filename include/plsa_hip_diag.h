@@ -81,6 +81,14 @@ int plsa_schedule_info(plsa_ctx *ctx, int32_t *xcd_lo /*[9]*/, double *xcd_end_u
  * stream, or PLSA_PACKED=0), -1 = not built yet.  csr: the document pass, csc: the column pass.  Any pointer may be NULL. */
 int plsa_packed_info(plsa_ctx *ctx, int32_t *csr, int32_t *csc);
 
+/* Lane shapes and gather widths of the fused passes for the factors in force (set_shape, table_is_wide in csrc/plsa_hip.hip):
+ * col = {lpn, ch, full} of the column pass (also the E-step, the log-likelihood and the reductions), row = {lpn, ch, full} of
+ * the document pass, full = (kp == 4 * lpn * ch); wide = {document pass, column pass}: 1 when that pass gathers its factor
+ * table (P(w|z), m rows / P(z|d), n rows) with 64-bit row addresses (a table of 4 GB or more, or PLSA_FORCE_WIDE).  A wide
+ * pass runs the run-time-kp instantiation whatever `full` says.  Tests read it to know which instantiations they reached.
+ * Any pointer may be NULL; fails before plsa_set_factors. */
+int plsa_pass_info(plsa_ctx *ctx, int32_t *col /*[3]*/, int32_t *row /*[3]*/, int32_t *wide /*[2]*/);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * HIP events on the context's own stream around every kernel launch (bench.py roofline figures).  */
 int plsa_timing_enable(plsa_ctx *ctx, int32_t on);
