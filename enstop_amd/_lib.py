@@ -1,4 +1,4 @@
-"""ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h).
+"""ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h and plsa_hip_members.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -105,6 +105,23 @@ SIGNATURES = {
     "plsa_synthetic_dominant_topics": (C.c_int, [_ctx, _i32p]),
 }
 
+# include/plsa_hip_members.h: batched ensemble members (a table of its own: SIGNATURES is the two headers above, exactly)
+_members = C.c_void_p
+MEMBERS_MAX = 64
+MEMBER_SIGNATURES = {
+    "plsa_members_create": (C.c_int, [_ctx, _i32, C.POINTER(_members)]),
+    "plsa_members_destroy": (None, [_members]),
+    "plsa_members_capacity": (C.c_int, [_ctx, _i32, C.POINTER(_i32)]),
+    "plsa_members_prepare": (C.c_int, [_members, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "plsa_members_fit": (C.c_int, [_members, _i32, _i32, _i32, C.c_double, C.c_float, _i32, _i32p, _vp, _i32, _i32p,
+                                   C.POINTER(_i32)]),
+    "plsa_members_copy_components": (C.c_int, [_members, _i32, C.c_void_p]),
+    "plsa_members_context": (C.c_int, [_members, _i32, C.POINTER(_ctx)]),
+    "plsa_members_info": (C.c_int, [_members, _i32, _i32p]),
+    "plsa_members_last_ll": (C.c_int, [_members, _i32, C.POINTER(C.c_double)]),
+    "plsa_members_release": (C.c_int, [_members]),
+}
+
 _lib = None
 HW_QUEUES = {"set_by": None, "hip_mapped_before_load": None}
 
@@ -154,7 +171,7 @@ def load():
             "(python -m enstop_amd.build). There is no CPU fallback." % LIB_PATH)
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1,6 +1,6 @@
 // plsa_hip.hip -- host side of libplsa_hip.so: context, HBM layout, kernel dispatch, EM drivers and
-// the C ABI declared in include/plsa_hip.h (the drop-in) and include/plsa_hip_diag.h (diagnostics, measurement, test
-// plumbing).  gfx950 only; no other back-end exists.
+// the C ABI declared in include/plsa_hip.h (the drop-in), include/plsa_hip_diag.h (diagnostics, measurement, test
+// plumbing) and include/plsa_hip_members.h (batched ensemble members: csrc/plsa_members.hpp).  gfx950 only; no other back-end exists.
 //
 // HBM layout per context (n docs, m words, k topics, kp = 4*ceil(k/4)):
 //   base CSR     indptr i32[n+1], col i32[nnz], val f32[nnz]      the uploaded corpus
@@ -31,8 +31,10 @@
 
 #include "../../include/plsa_hip.h"
 #include "../../include/plsa_hip_diag.h"
+#include "../../include/plsa_hip_members.h"
 #include "mt_jump.hpp"
 #include "plsa_kernels.hpp"
+#include "plsa_member_kernels.hpp"
 #include "plsa_ref_kernels.hpp"
 #include "plsa_synth.hpp"
 
@@ -1788,6 +1790,42 @@ bool stop_test(float cur, float &prev, double tol, bool zero_arm = true) {
     return false;
 }
 
+// the PLSA_* knobs a context reads when it is created (a member context of a batch reads them like its leader)
+void read_knobs(plsa_ctx *c) {
+    if (const char *s = getenv("PLSA_OVERLAP")) c->overlap = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_OVERLAP_FULL_LIMIT")) c->overlap_full_limit = atof(s);
+    if (const char *s = getenv("PLSA_ROW_ITEMS")) c->ritems_mode = atoi(s);
+    if (const char *s = getenv("PLSA_PACKED")) c->packed = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_ROW_SEG")) c->rseg_override = std::max(1, atoi(s));
+    int mult = 128;  // blocks per CU a grid may hold: large (but bounded) grids measured best (DESIGN.md)
+    if (const char *s = getenv("PLSA_GRID_MULT")) mult = std::max(1, atoi(s));
+    c->grid_cap = c->prop.multiProcessorCount * mult;
+    if (const char *s = getenv("PLSA_CONTIG")) g_contig = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_PLACEMENT_CANDIDATES")) c->placement_candidates = std::max(1, atoi(s));
+    if (const char *s = getenv("PLSA_COL_SEG")) c->seg_override = std::max(1, atoi(s));
+    if (const char *s = getenv("PLSA_HEAVY_ITEMS")) c->heavy_items = std::max(1, atoi(s));
+    if (const char *s = getenv("PLSA_SORT_ROWS")) c->sort_rows = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_ROW_XCD")) c->row_xcd = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_ITEM_ORDER")) c->use_item_order = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_XCD_SPLIT")) c->xcd_split = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_BALANCE")) c->balance = atoi(s);
+    if (const char *s = getenv("PLSA_ORDER_BAND")) c->order_band = atoi(s);
+    if (const char *s = getenv("PLSA_GRAPH")) c->graph = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_PIPELINE")) c->pipeline = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_CHUNKS_PER_LANE")) c->chunks_per_lane = atoi(s);
+    if (const char *s = getenv("PLSA_E_ROWS")) c->e_rows = atoi(s);
+    if (const char *s = getenv("PLSA_E_SEG")) c->eseg_override = atoi(s);
+    if (const char *s = getenv("PLSA_MT_STREAMS")) c->mt_streams = std::max(1, std::min(4096, atoi(s)));
+    if (const char *s = getenv("PLSA_MT_MIN_BLOCKS")) c->mt_min_blocks = std::max(1, atoi(s));
+    if (const char *s = getenv("PLSA_SMALL_GRID")) c->small_grid = std::max(0, atoi(s));
+    if (const char *s = getenv("PLSA_ROW_SHAPE")) c->row_shape_8x2 = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_FORCE_WIDE")) c->force_wide = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_MT_CHAIN")) c->mt_chain = atoi(s) != 0;
+    if (const char *s = getenv("PLSA_SPECULATE")) c->speculate = atoi(s);
+    if (const char *s = getenv("PLSA_REF_CHAIN"))      // norm_pwz of the reference arithmetic: auto (default) | pairs | serial
+        c->ref_chain_mode = !strcmp(s, "pairs") ? 1 : (!strcmp(s, "serial") ? 2 : 0);
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1835,38 +1873,7 @@ int plsa_create(int device, plsa_ctx **out) {
         host_alloc(c->h_ll, 2) != hipSuccess)
         return fail(nullptr, "stream / pinned buffer creation failed");
     c->ls = c->stream;
-    if (const char *s = getenv("PLSA_OVERLAP")) c->overlap = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_OVERLAP_FULL_LIMIT")) c->overlap_full_limit = atof(s);
-    if (const char *s = getenv("PLSA_ROW_ITEMS")) c->ritems_mode = atoi(s);
-    if (const char *s = getenv("PLSA_PACKED")) c->packed = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_ROW_SEG")) c->rseg_override = std::max(1, atoi(s));
-    int mult = 128;  // blocks per CU a grid may hold: large (but bounded) grids measured best (DESIGN.md)
-    if (const char *s = getenv("PLSA_GRID_MULT")) mult = std::max(1, atoi(s));
-    c->grid_cap = c->prop.multiProcessorCount * mult;
-    if (const char *s = getenv("PLSA_CONTIG")) g_contig = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_PLACEMENT_CANDIDATES")) c->placement_candidates = std::max(1, atoi(s));
-    if (const char *s = getenv("PLSA_COL_SEG")) c->seg_override = std::max(1, atoi(s));
-    if (const char *s = getenv("PLSA_HEAVY_ITEMS")) c->heavy_items = std::max(1, atoi(s));
-    if (const char *s = getenv("PLSA_SORT_ROWS")) c->sort_rows = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_ROW_XCD")) c->row_xcd = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_ITEM_ORDER")) c->use_item_order = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_XCD_SPLIT")) c->xcd_split = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_BALANCE")) c->balance = atoi(s);
-    if (const char *s = getenv("PLSA_ORDER_BAND")) c->order_band = atoi(s);
-    if (const char *s = getenv("PLSA_GRAPH")) c->graph = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_PIPELINE")) c->pipeline = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_CHUNKS_PER_LANE")) c->chunks_per_lane = atoi(s);
-    if (const char *s = getenv("PLSA_E_ROWS")) c->e_rows = atoi(s);
-    if (const char *s = getenv("PLSA_E_SEG")) c->eseg_override = atoi(s);
-    if (const char *s = getenv("PLSA_MT_STREAMS")) c->mt_streams = std::max(1, std::min(4096, atoi(s)));
-    if (const char *s = getenv("PLSA_MT_MIN_BLOCKS")) c->mt_min_blocks = std::max(1, atoi(s));
-    if (const char *s = getenv("PLSA_SMALL_GRID")) c->small_grid = std::max(0, atoi(s));
-    if (const char *s = getenv("PLSA_ROW_SHAPE")) c->row_shape_8x2 = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_FORCE_WIDE")) c->force_wide = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_MT_CHAIN")) c->mt_chain = atoi(s) != 0;
-    if (const char *s = getenv("PLSA_SPECULATE")) c->speculate = atoi(s);
-    if (const char *s = getenv("PLSA_REF_CHAIN"))      // norm_pwz of the reference arithmetic: auto (default) | pairs | serial
-        c->ref_chain_mode = !strcmp(s, "pairs") ? 1 : (!strcmp(s, "serial") ? 2 : 0);
+    read_knobs(c);
     *out = owner.release();
     return 0;
 }
@@ -3328,3 +3335,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 }
 
 }  // extern "C"
+
+#include "plsa_members.hpp"   // batched ensemble members (include/plsa_hip_members.h)

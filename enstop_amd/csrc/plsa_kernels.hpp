@@ -363,8 +363,10 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_e_step_rows(const int *__re
 // together; entries beyond the row end are padded with (word 0, count 0) and add exact zeros.
 // S = Packed<...> (fused only): `colidx` is the packed entry stream, `vals` is read for escaped entries only.
 // ------------------------------------------------------------------------------------------------
-template <class S, bool FROM_P, bool WANT_LL, bool TINY = false>
-__global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restrict__ indptr,
+// `block` of `nblocks`: the caller's position in the grid that partitions the work (the launch's own for k_row_pass, the
+// member's standalone grid for k_row_pass_members: the log-likelihood leaves one double per workgroup of THAT grid)
+template <class S, bool FROM_P, bool WANT_LL, bool TINY>
+__device__ __forceinline__ void row_pass_body(const int *__restrict__ indptr,
                                                   const int *__restrict__ colidx,
                                                   const float *__restrict__ vals, int n,
                                                   const int *__restrict__ row_order,
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restr
                                                   float thresh, double *__restrict__ ll_partials,
                                                   const int *__restrict__ ritem_row,
                                                   const int *__restrict__ ritem_start, int rseg,
-                                                  i64 n_ritems, float *__restrict__ rpartial, int xcd_rows) {
+                                                  i64 n_ritems, float *__restrict__ rpartial, int xcd_rows, unsigned block, unsigned nblocks) {
     constexpr int LPN = S::LPN, CH = S::CH, UNR = S::UNR;
     constexpr int GPB = 256 / LPN;  // groups per block
     const int kp = S::kp(kp_rt);
@@ -387,14 +389,14 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restr
     // xcd_rows (PLSA_ROW_XCD, experiment): workgroup b runs on XCD b % 8; XCD x takes the x-th EIGHTH of the visiting list
     // (the grid covers the list in one trip and is a multiple of 8), so that an XCD's L2 sees the P(w|z) rows of one
     // contiguous range of documents only -- worth something when neighbouring documents share vocabulary
-    const i64 first_block = xcd_rows ? (i64)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : (i64)blockIdx.x;
+    const i64 first_block = xcd_rows ? (i64)(block & 7) * (nblocks >> 3) + (block >> 3) : (i64)block;
     constexpr bool tiny = !FROM_P && TINY;
     // item mode (ritem_row != nullptr): rows are cut into items of <= rseg entries, a group owns
     // one item and writes an un-normalised partial row that k_row_reduce adds up in item order.
     // Used when there are too few / too uneven rows to fill the chip (few long documents).
     const bool items = ritem_row != nullptr;
     const i64 n_work = items ? n_ritems : (i64)n;
-    for (i64 r = first_block * GPB + gid; r < n_work; r += (i64)gridDim.x * GPB) {
+    for (i64 r = first_block * GPB + gid; r < n_work; r += (i64)nblocks * GPB) {
         const int d = items ? ritem_row[r] : (row_order ? row_order[r] : (int)r);
         const int j0 = items ? ritem_start[r] : indptr[d];
         const int j1 = items ? min(j0 + rseg, indptr[d + 1]) : indptr[d + 1];
@@ -515,23 +517,43 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restr
             if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
             __syncthreads();
         }
-        if (threadIdx.x == 0) ll_partials[blockIdx.x] = red[0];
+        if (threadIdx.x == 0) ll_partials[block] = red[0];
     }
+}
+
+template <class S, bool FROM_P, bool WANT_LL, bool TINY = false>
+__global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restrict__ indptr,
+                                                  const int *__restrict__ colidx,
+                                                  const float *__restrict__ vals, int n,
+                                                  const int *__restrict__ row_order,
+                                                  const float *__restrict__ U,
+                                                  const float *__restrict__ Vt,
+                                                  const float *__restrict__ P,
+                                                  float *__restrict__ U_new,
+                                                  const float *__restrict__ sw,
+                                                  float *__restrict__ norm_pdz_out, int kp_rt,
+                                                  float thresh, double *__restrict__ ll_partials,
+                                                  const int *__restrict__ ritem_row,
+                                                  const int *__restrict__ ritem_start, int rseg,
+                                                  i64 n_ritems, float *__restrict__ rpartial, int xcd_rows) {
+    row_pass_body<S, FROM_P, WANT_LL, TINY>(indptr, colidx, vals, n, row_order, U, Vt, P, U_new, sw, norm_pdz_out, kp_rt, thresh,
+                                            ll_partials, ritem_row, ritem_start, rseg, n_ritems, rpartial, xcd_rows,
+                                            blockIdx.x, gridDim.x);
 }
 
 // k_row_reduce: adds the item partials of each document (fixed order), then norm_pdz and the
 // division (plsa.py:194, 200-202) -- the tail of k_row_pass for the item mode.
 template <class S>
-__global__ __launch_bounds__(256) void k_row_reduce(const int *__restrict__ ritem_first, int n,
-                                                    const float *__restrict__ rpartial,
-                                                    float *__restrict__ U_new,
-                                                    float *__restrict__ norm_pdz_out, int kp_rt) {
+__device__ __forceinline__ void row_reduce_body(const int *__restrict__ ritem_first, int n,
+                                                const float *__restrict__ rpartial,
+                                                float *__restrict__ U_new,
+                                                float *__restrict__ norm_pdz_out, int kp_rt, unsigned block, unsigned nblocks) {
     constexpr int LPN = S::LPN, CH = S::CH;
     constexpr int GPB = 256 / LPN;
     const int kp = S::kp(kp_rt);
     const int li = threadIdx.x % LPN;
     const int gid = threadIdx.x / LPN;
-    for (i64 d = (i64)blockIdx.x * GPB + gid; d < n; d += (i64)gridDim.x * GPB) {
+    for (i64 d = (i64)block * GPB + gid; d < n; d += (i64)nblocks * GPB) {
         const int i0 = ritem_first[d], i1 = ritem_first[d + 1];
         float4 acc[CH];
 #pragma unroll
@@ -558,6 +580,14 @@ __global__ __launch_bounds__(256) void k_row_reduce(const int *__restrict__ rite
             }
         }
     }
+}
+
+template <class S>
+__global__ __launch_bounds__(256) void k_row_reduce(const int *__restrict__ ritem_first, int n,
+                                                    const float *__restrict__ rpartial,
+                                                    float *__restrict__ U_new,
+                                                    float *__restrict__ norm_pdz_out, int kp_rt) {
+    row_reduce_body<S>(ritem_first, n, rpartial, U_new, norm_pdz_out, kp_rt, blockIdx.x, gridDim.x);
 }
 
 __global__ void k_ritem_fill(const int *__restrict__ indptr, const int *__restrict__ ritem_first, int n,
@@ -675,8 +705,8 @@ __device__ __forceinline__ void col_batch(int s0, int d_l, float x_l, int p_l, i
 // (round 3: 2.35 -> 2.06 ms at config 3 with 256-entry items, 1.93 ms with 128).
 // Per chunk the workgroup also writes the float64 sum of its GPB accumulators (`chunk_sums`, the rows norm_pwz is
 // added up from, in chunk order): every result is independent of the boundaries and of the grid.
-template <class S, bool FROM_P, bool TIMED, bool TINY = false>
-__global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__restrict__ item_rec, i64 n_items,
+template <class S, bool FROM_P, bool TIMED, bool TINY>
+__device__ __forceinline__ void col_pass_body(const int4 *__restrict__ item_rec, i64 n_items,
                                                   const int *__restrict__ xcd_lo,
                                                   const int *__restrict__ csc_row,
                                                   const float *__restrict__ csc_val,
@@ -687,19 +717,18 @@ __global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__
                                                   const float *__restrict__ sw,
                                                   float *__restrict__ partial, int kp_rt, float thresh,
                                                   int xcd_split, double *__restrict__ chunk_sums,
-                                                  unsigned long long *__restrict__ t_end) {
+                                                  unsigned long long *__restrict__ t_end, double *scol /*[GPB][kp]*/, unsigned block, unsigned nblocks) {
     constexpr int LPN = S::LPN, CH = S::CH, UNR = S::UNR_COL;
     constexpr int GPB = 256 / LPN;
-    extern __shared__ double scol[];   // [GPB][kp]: sum of the chunk's accumulators (-> norm_pwz)
     const int kp = S::kp(kp_rt);
     const int li = threadIdx.x % LPN;
     const int gid = threadIdx.x / LPN;
     const int n_chunks = (int)((n_items + GPB - 1) / GPB);
-    const int xcd = xcd_split ? (int)(blockIdx.x & 7) : 0;
-    const int nq = xcd_split ? (int)((gridDim.x + 7 - xcd) / 8) : (int)gridDim.x;   // workgroups on this XCD
-    const int q = xcd_split ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int xcd = xcd_split ? (int)(block & 7) : 0;
+    const int nq = xcd_split ? (int)((nblocks + 7 - xcd) / 8) : (int)nblocks;   // workgroups on this XCD
+    const int q = xcd_split ? (int)(block >> 3) : (int)block;
     const int c_lo = xcd_split ? xcd_lo[xcd] : 0, c_hi = xcd_split ? xcd_lo[xcd + 1] : n_chunks;
-    if (TIMED && blockIdx.x == 0 && threadIdx.x == 0) t_end[gridDim.x] = wall_clock64();   // launch start
+    if (TIMED && block == 0 && threadIdx.x == 0) t_end[nblocks] = wall_clock64();   // launch start
     for (int chunk = c_lo + q; chunk < c_hi; chunk += nq) {
         const i64 io = (i64)chunk * GPB + gid;
         float4 acc[CH];
@@ -740,7 +769,25 @@ __global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__
         block_colsum<S>(acc, li, gid, kp, scol, chunk_sums + (i64)chunk * kp);
         __syncthreads();               // scol is rewritten by the next chunk
     }
-    if (TIMED && threadIdx.x == 0) t_end[blockIdx.x] = wall_clock64();
+    if (TIMED && threadIdx.x == 0) t_end[block] = wall_clock64();
+}
+
+template <class S, bool FROM_P, bool TIMED, bool TINY = false>
+__global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__restrict__ item_rec, i64 n_items,
+                                                  const int *__restrict__ xcd_lo,
+                                                  const int *__restrict__ csc_row,
+                                                  const float *__restrict__ csc_val,
+                                                  const int *__restrict__ csc_pos,
+                                                  const float *__restrict__ U,
+                                                  const float *__restrict__ Vt,
+                                                  const float *__restrict__ P,
+                                                  const float *__restrict__ sw,
+                                                  float *__restrict__ partial, int kp_rt, float thresh,
+                                                  int xcd_split, double *__restrict__ chunk_sums,
+                                                  unsigned long long *__restrict__ t_end) {
+    extern __shared__ double scol[];   // [GPB][kp]: sum of the chunk's accumulators (-> norm_pwz)
+    col_pass_body<S, FROM_P, TIMED, TINY>(item_rec, n_items, xcd_lo, csc_row, csc_val, csc_pos, U, Vt, P, sw, partial, kp_rt, thresh,
+                                          xcd_split, chunk_sums, t_end, scol, blockIdx.x, gridDim.x);
 }
 
 // visiting-order item records of the column pass: rec[io] = {column, first entry, end, item id (partial slot)}
@@ -957,11 +1004,11 @@ __global__ __launch_bounds__(256) void k_colsum_final(const double *__restrict__
 
 // stage 1 of norm_pwz from the column pass' per-block sums: `rows` rows of kp doubles -> gridDim.x rows
 // (block b adds rows b*per .. in strand order; same thread layout as colsum_slab_body)
-__global__ __launch_bounds__(256) void k_norm_reduce(const double *__restrict__ in, int rows, int kp,
-                                                     double *__restrict__ out) {
-    __shared__ double sred[256];
-    const i64 per = ((i64)rows + gridDim.x - 1) / gridDim.x;
-    const i64 r0 = (i64)blockIdx.x * per, r1 = min((i64)rows, r0 + per);
+__device__ __forceinline__ void norm_reduce_body(const double *__restrict__ in, int rows, int kp,
+                                                 double *__restrict__ out, double *sred /*[256]*/, unsigned block,
+                                                 unsigned nblocks) {
+    const i64 per = ((i64)rows + nblocks - 1) / nblocks;
+    const i64 r0 = (i64)block * per, r1 = min((i64)rows, r0 + per);
     for (int zb = 0; zb < kp; zb += 256) {
         const int span = min(256, kp - zb);
         const int rpp = 256 / span;
@@ -977,10 +1024,16 @@ __global__ __launch_bounds__(256) void k_norm_reduce(const double *__restrict__ 
         if ((int)threadIdx.x < span) {
             double tot = 0.0;
             for (int r = 0; r < rpp; ++r) tot += sred[r * span + threadIdx.x];
-            out[(i64)blockIdx.x * kp + zb + threadIdx.x] = tot;
+            out[(i64)block * kp + zb + threadIdx.x] = tot;
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(256) void k_norm_reduce(const double *__restrict__ in, int rows, int kp,
+                                                     double *__restrict__ out) {
+    __shared__ double sred[256];
+    norm_reduce_body(in, rows, kp, out, sred, blockIdx.x, gridDim.x);
 }
 
 // division by norm_pwz (snorm: LDS copy), plsa.py:196-199
@@ -1010,8 +1063,8 @@ __global__ __launch_bounds__(256) void k_v_normalise(const float *__restrict__ V
 }
 
 // final, fixed-order sum of the per-block log-likelihood partials
-__global__ void k_ll_final(const double *__restrict__ partials, int nb, double *__restrict__ out) {
-    __shared__ double red[256];
+__device__ __forceinline__ void ll_final_body(const double *__restrict__ partials, int nb, double *__restrict__ out,
+                                              double *red /*[256]*/) {
     double s = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) s += partials[i];
     red[threadIdx.x] = s;
@@ -1021,6 +1074,11 @@ __global__ void k_ll_final(const double *__restrict__ partials, int nb, double *
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = red[0];
+}
+
+__global__ void k_ll_final(const double *__restrict__ partials, int nb, double *__restrict__ out) {
+    __shared__ double red[256];
+    ll_final_body(partials, nb, out, red);
 }
 
 // standalone log-likelihood, plsa.py:375-384 (row-owned; same traversal as k_row_pass)

@@ -1,0 +1,455 @@
+// plsa_members.hpp -- host side of the batched ensemble members (include/plsa_hip_members.h); part of plsa_hip.hip's
+// translation unit (included at its end: it uses the context, the builders and the launch helpers defined there).
+//
+// Layout of a batch.  Every member slot is a plsa_ctx of its own that BORROWS the leader's streams and base corpus:
+// its resample, CSC items, packed streams, row items / row order, lane shape and factors are built by the code a
+// standalone fit runs (plsa_bootstrap, mt_init / plsa_set_factors, ensure_*), with the member's own n, nnz and kp -- so
+// item lengths, the row-item decision, heavy-column lists and chunk boundaries are the standalone ones by construction.
+// The builders' scratch (tmp0..2, cubtmp, the MT19937 words) is the LEADER's, lent for the duration of a call.
+// plsa_members_fit then groups the members by kernel instantiation (packed column stream, packed document stream), fills
+// one plsa::MemberArgs per member and runs the fused schedule with one launch per kernel and group
+// (plsa_member_kernels.hpp); a group of one, and every member of an ineligible call, goes through plsa_fit.
+#pragma once
+
+struct plsa_members {
+    struct MemberDelete {
+        void operator()(plsa_ctx *m) const {
+            if (!m) return;
+            m->stream.h = nullptr; m->stream2.h = nullptr;        // the leader's
+            delete m;                                             // (borrowed DevBufs are not freed)
+        }
+    };
+    using Member = std::unique_ptr<plsa_ctx, MemberDelete>;
+    plsa_ctx *leader = nullptr;
+    std::vector<Member> ctx;
+    std::vector<char> prepared;
+    struct Info { int group = -1, group_size = 0, items = 0, rseg = 0, n_chunks = 0, n_heavy = 0, row_grid = 0, norm_blocks = 0; };
+    std::vector<Info> info;
+    std::vector<double> last_ll;     // the float64 likelihood of each member's last test (plsa_members_last_ll)
+    DevBuf table, ll_out;            // plsa::MemberArgs[n], double[n]
+    Pinned<double> h_ll;
+};
+
+namespace {
+
+int new_member(plsa_ctx *leader, plsa_members::Member &out) {
+    plsa_members::Member m(new plsa_ctx());
+    m->device = leader->device;
+    m->prop = leader->prop;
+    m->stream.h = leader->stream.h;
+    m->stream2.h = leader->stream2.h;
+    m->ls = m->stream;
+    if (hipEventCreateWithFlags(&m->ev_fork.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&m->ev_join.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&m->ev_row.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&m->ev_tail.h, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&m->ev_ll.h, hipEventDisableTiming) != hipSuccess ||
+        host_alloc(m->h_ll, 2) != hipSuccess)
+        return fail(leader, "plsa_members: event / pinned buffer creation failed");
+    read_knobs(m.get());
+    out = std::move(m);
+    return 0;
+}
+
+// the leader's builder scratch serves the member for the duration of a call (everything runs on the one shared stream)
+struct ScratchLoan {
+    plsa_ctx *l, *m;
+    void swap_all() {
+        for (auto p : {&plsa_ctx::tmp0, &plsa_ctx::tmp1, &plsa_ctx::tmp2, &plsa_ctx::cubtmp, &plsa_ctx::pk_count, &plsa_ctx::mt_words,
+                       &plsa_ctx::mt_state, &plsa_ctx::mt_fin, &plsa_ctx::mt_poly, &plsa_ctx::mt_seq})
+            (l->*p).swap(m->*p);
+    }
+    ScratchLoan(plsa_ctx *l_, plsa_ctx *m_) : l(l_), m(m_) { swap_all(); }
+    ~ScratchLoan() { swap_all(); }
+};
+
+// a member's failure is reported through the leader (plsa_last_error of the batch's context)
+int member_rc(plsa_ctx *leader, plsa_ctx *m, int rc) {
+    if (rc) leader->err = m->err;
+    return rc;
+}
+
+int members_check(plsa_members *b, int32_t member) {
+    if (!b) return fail(nullptr, "plsa_members: NULL batch");
+    if (member < 0 || member >= (int32_t)b->ctx.size())
+        return fail(b->leader, "plsa_members: member %d outside [0, %d)", member, (int)b->ctx.size());
+    return 0;
+}
+
+// the structures and buffers of one member's fused iteration, as the standalone wrappers (run_row_pass, run_col_pass,
+// run_col_tail) ensure them, and the member's standalone grids -> one table row
+int member_args(plsa_ctx *c, double *ll_out, plsa::MemberArgs &a, plsa_members::Info &inf) {
+    CHK(ensure_packed_csc(c));
+    CHK(ensure_packed_csr(c));
+    CHK(ensure_ritems(c));
+    const bool items = c->ritems.use && c->ritems.n > 0;
+    const int *order = nullptr;
+    if (!items) CHK(ensure_roworder(c, &order));
+    const int row_grid = grid_for(c, items ? c->ritems.n : c->n, 256 / c->row_lpn);
+    if (items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->ritems.n * c->kp));
+    CHK(ensure(c, c->ll_partials, sizeof(double) * (size_t)row_grid));
+    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->csc.n_items, 1) * c->kp));
+    const int gpb = 256 / c->lpn;
+    const int n_chunks = (int)((c->csc.n_items + gpb - 1) / gpb);
+    CHK(ensure(c, c->colsum_rows, sizeof(double) * (size_t)std::max(n_chunks, 1) * c->kp));
+    CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
+    int norm_blocks = 0;
+    if (n_chunks > 2048) {           // run_col_tail: two stages
+        norm_blocks = std::max(64, std::min(1024, n_chunks / 64));
+        CHK(ensure(c, c->colsum_rows2, sizeof(double) * (size_t)norm_blocks * c->kp));
+    }
+    const bool pk_col = c->packed && c->pk_csc.ok, pk_row = c->packed && c->pk_csr.ok;
+    a = plsa::MemberArgs{};
+    a.item_rec = c->csc.item_rec.as<int4>();
+    a.csc_row = pk_col ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
+    a.csc_val = c->csc.val.as<float>();
+    a.partial = c->partial.as<float>();
+    a.chunk_sums = c->colsum_rows.as<double>();
+    a.n_items = c->csc.n_items;
+    a.chunk_sums2 = c->colsum_rows2.as<double>();
+    a.norm_pwz = c->norm_pwz.as<float>();
+    a.item_first = c->csc.item_first.as<int>();
+    a.heavy_cols = c->csc.heavy_cols.as<int>();
+    a.n_chunks = n_chunks;
+    a.norm_blocks = norm_blocks;
+    a.m = (int)c->m;
+    a.n_heavy = c->csc.n_heavy;
+    a.heavy_items = c->heavy_items;
+    a.reduce_grid = grid_for(c, c->m, gpb) + c->csc.n_heavy;
+    a.indptr = c->indptr;
+    a.colidx = pk_row ? c->pk_csr.buf.as<int>() : c->col;
+    a.vals = c->val;
+    a.row_order = order;
+    a.ritem_row = items ? c->ritems.row.as<int>() : nullptr;
+    a.ritem_start = items ? c->ritems.start.as<int>() : nullptr;
+    a.ritem_first = items ? c->ritems.first.as<int>() : nullptr;
+    a.rpartial = items ? c->rpartial.as<float>() : nullptr;
+    a.ll_partials = c->ll_partials.as<double>();
+    a.ll_out = ll_out;
+    a.n_ritems = c->ritems.n;
+    a.n = (int)c->n;
+    a.rseg = c->ritems.seg;
+    a.row_grid = row_grid;
+    a.row_reduce_grid = grid_for(c, c->n, 256 / c->row_lpn);
+    for (int i = 0; i < 2; ++i) { a.U[i] = c->U[i].as<float>(); a.Vt[i] = c->Vt[i].as<float>(); }
+    inf.items = items; inf.rseg = c->ritems.seg; inf.n_chunks = n_chunks; inf.n_heavy = c->csc.n_heavy;
+    inf.row_grid = row_grid; inf.norm_blocks = norm_blocks;
+    c->colsum_rows_used = n_chunks;
+    return 0;
+}
+
+// lane shape of the document pass, 32-bit gather offsets only (a batch carries no wide table)
+template <class Fn>
+int dispatch_narrow_row(plsa_ctx *c, Fn &&fn) {
+    if (c->row_lpn == 8 && c->row_ch == 2 && c->kp == 64) { fn(plsa::Shape<8, 2, true>{}); return 0; }
+    return dispatch_shape(c, fn);
+}
+
+// The fused schedule of plsa_fit for the members `who` (one instantiation group), every kernel launched once for all of
+// them.  All live members are at the same iteration, so whether a pass carries the likelihood (the initial one on the
+// first document pass, a due test later) is the same for all; the TEST is per member.
+int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<plsa::MemberArgs> &rows, int n_iter,
+              int n_iter_per_test, double tolerance, float thresh, int flags, int32_t *iters_done, float *ll_trace, int ll_cap,
+              int32_t *n_ll) {
+    plsa_ctx *L = b->leader, *c0 = b->ctx[who[0]].get();
+    const int G = (int)who.size();
+    const bool trace = flags & PLSA_TRACE_LL, zero_arm = !(flags & PLSA_STOP_NO_ZERO_ARM);
+    HIPCHK(L, hipMemcpyAsync(b->table.p, rows.data(), sizeof(plsa::MemberArgs) * (size_t)G, hipMemcpyHostToDevice, L->stream));
+    HIPCHK(L, hipStreamSynchronize(L->stream));      // (`rows` is the caller's; and the members' builders have finished)
+    const plsa::MemberArgs *table = b->table.as<plsa::MemberArgs>();
+    int row_x = 1, reduce_x = 1, chunks_x = 1, norm_x = 0, rr_x = 0;
+    for (const auto &a : rows) {
+        row_x = std::max(row_x, a.row_grid);
+        reduce_x = std::max(reduce_x, a.reduce_grid);
+        chunks_x = std::max(chunks_x, a.n_chunks);
+        norm_x = std::max(norm_x, a.norm_blocks);
+        if (a.ritem_row) rr_x = std::max(rr_x, a.row_reduce_grid);
+    }
+    const bool pk_row = c0->packed && c0->pk_csr.ok, pk_col = c0->packed && c0->pk_csc.ok;
+    const bool tiny = thresh < plsa::TINY_THRESH;
+    const int kp = c0->kp;
+    using u64 = unsigned long long;
+    u64 live = G == 64 ? ~0ull : ((1ull << G) - 1ull), cu = 0, cv = 0;
+    for (int g = 0; g < G; ++g) {
+        plsa_ctx *c = b->ctx[who[g]].get();
+        if (c->cu) cu |= 1ull << g;
+        if (c->cv) cv |= 1ull << g;
+    }
+    using T = std::true_type;
+    using F = std::false_type;
+    // The two halves of an iteration read the same current factors and write disjoint outputs: the column chain runs on
+    // the leader's second stream underneath the document pass (fork / join per iteration, like plsa_fit's small-corpus form)
+    const bool two_streams = L->overlap;
+    hipStream_t col_stream = two_streams ? L->stream2.h : L->stream.h;
+    auto row_pass = [&](bool want_ll) -> int {
+        CHK(dispatch_narrow_row(c0, [&](auto S) {
+            using Sh = decltype(S);
+            auto launch = [&](auto SS, auto LL, auto TN) {
+                hipLaunchKernelGGL((plsa::k_row_pass_members<decltype(SS), decltype(LL)::value, decltype(TN)::value>),
+                                   dim3(row_x, G), dim3(256), 0, L->stream, table, live, cu, cv, kp, thresh);
+            };
+            auto go = [&](auto LL, auto TN) { if (pk_row) launch(plsa::Packed<Sh>{}, LL, TN); else launch(Sh{}, LL, TN); };
+            if (want_ll) { if (tiny) go(T{}, T{}); else go(T{}, F{}); }
+            else { if (tiny) go(F{}, T{}); else go(F{}, F{}); }
+            if (rr_x > 0)
+                hipLaunchKernelGGL((plsa::k_row_reduce_members<Sh>), dim3(rr_x, G), dim3(256), 0, L->stream, table, live, cu, kp);
+        }));
+        if (want_ll) {
+            hipLaunchKernelGGL(plsa::k_ll_final_members, dim3(G), dim3(256), 0, L->stream, table, live);
+            HIPCHK(L, hipMemcpyAsync(b->h_ll.get(), b->ll_out.p, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, L->stream));
+        }
+        return launch_check(L, "k_row_pass_members");
+    };
+    auto col_chain = [&]() -> int {
+        CHK(dispatch_shape(c0, [&](auto S) {
+            using Sh = decltype(S);
+            constexpr int GPB = 256 / Sh::LPN;
+            const size_t smem = sizeof(double) * (size_t)GPB * kp;
+            auto launch = [&](auto SS, auto TN) {
+                hipLaunchKernelGGL((plsa::k_col_pass_members<decltype(SS), decltype(TN)::value>), dim3(chunks_x, G), dim3(256),
+                                   smem, col_stream, table, live, cu, cv, kp, thresh);
+            };
+            auto go = [&](auto TN) { if (pk_col) launch(plsa::Packed<Sh>{}, TN); else launch(Sh{}, TN); };
+            if (tiny) go(T{}); else go(F{});
+            if (norm_x > 0)
+                hipLaunchKernelGGL(plsa::k_norm_reduce_members, dim3(norm_x, G), dim3(256), 0, col_stream, table, live, kp);
+            hipLaunchKernelGGL(plsa::k_colsum_final_members, dim3(G), dim3(256), 0, col_stream, table, live, kp);
+            hipLaunchKernelGGL((plsa::k_col_reduce_norm_members<Sh>), dim3(reduce_x, G), dim3(256),
+                               sizeof(float) * (size_t)(GPB + 1) * kp, col_stream, table, live, cv, kp);
+        }));
+        return launch_check(L, "k_col_pass_members");
+    };
+    std::vector<float> prev(G, 0.f);
+    std::vector<int> nll(G, 0), iters(G, 0);
+    auto record = [&](int g, float v) {
+        if (ll_trace && nll[g] < ll_cap) ll_trace[(size_t)who[g] * ll_cap + nll[g]] = v;
+        nll[g]++;
+    };
+    bool pending = false, first = true;
+    for (int i = 0; i < n_iter && live; ++i) {
+        const bool want_ll = pending || first;
+        if (two_streams) {
+            HIPCHK(L, hipEventRecord(L->ev_fork, L->stream));
+            HIPCHK(L, hipStreamWaitEvent(L->stream2, L->ev_fork, 0));
+        }
+        CHK(col_chain());
+        if (two_streams) HIPCHK(L, hipEventRecord(L->ev_join, L->stream2));
+        CHK(row_pass(want_ll));
+        if (two_streams) HIPCHK(L, hipStreamWaitEvent(L->stream, L->ev_join, 0));
+        if (want_ll) {
+            HIPCHK(L, hipStreamSynchronize(L->stream));
+            for (int g = 0; g < G; ++g) {
+                if (!((live >> g) & 1ull)) continue;
+                const float cur = (float)b->h_ll[g];
+                b->last_ll[who[g]] = b->h_ll[g];
+                if (first) { prev[g] = cur; record(g, cur); continue; }
+                record(g, cur);
+                if (stop_test(cur, prev[g], tolerance, zero_arm)) live &= ~(1ull << g);    // this pass is discarded: no swap
+            }
+            first = false;
+        }
+        cu ^= live; cv ^= live;
+        for (int g = 0; g < G; ++g) if ((live >> g) & 1ull) iters[g]++;
+        pending = (i % n_iter_per_test == 0);
+    }
+    HIPCHK(L, hipStreamSynchronize(L->stream));
+    for (int g = 0; g < G; ++g) {
+        plsa_ctx *c = b->ctx[who[g]].get();
+        c->cu = (int)((cu >> g) & 1ull); c->cv = (int)((cv >> g) & 1ull);
+        c->p_state.invalidate();
+        if (((live >> g) & 1ull) && pending && trace) {      // test of the last iteration: result-neutral (plsa_fit)
+            ScratchLoan loan(L, c);
+            double ll = 0.0;
+            CHK(member_rc(L, c, run_loglik(c, nullptr, &ll)));
+            b->last_ll[who[g]] = ll;
+            record(g, (float)ll);
+        }
+        iters_done[who[g]] = iters[g];
+        n_ll[who[g]] = nll[g];
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plsa_members_create(plsa_ctx *ctx, int32_t n_members, plsa_members **out) {
+    if (!out) return fail(ctx, "plsa_members_create: out is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(nullptr, "plsa_members_create: NULL context");
+    if (n_members < 1 || n_members > PLSA_MEMBERS_MAX)
+        return fail(ctx, "plsa_members_create: n_members=%d outside [1, %d]", n_members, (int)PLSA_MEMBERS_MAX);
+    static_assert(PLSA_MEMBERS_MAX == plsa::MEMBERS_MAX, "the live mask is one 64-bit word");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<plsa_members> b(new plsa_members());
+    b->leader = ctx;
+    b->ctx.resize(n_members);
+    b->prepared.assign(n_members, 0);
+    b->info.assign(n_members, plsa_members::Info{});
+    b->last_ll.assign(n_members, 0.0);
+    for (auto &m : b->ctx) CHK(new_member(ctx, m));
+    CHK(ensure(ctx, b->table, sizeof(plsa::MemberArgs) * (size_t)n_members));
+    CHK(ensure(ctx, b->ll_out, sizeof(double) * (size_t)n_members));
+    if (host_alloc(b->h_ll, (size_t)n_members) != hipSuccess) return fail(ctx, "plsa_members_create: pinned buffer allocation failed");
+    *out = b.release();
+    return 0;
+}
+
+void plsa_members_destroy(plsa_members *b) {
+    if (!b) return;
+    (void)hipSetDevice(b->leader->device);
+    (void)hipStreamSynchronize(b->leader->stream);
+    (void)hipStreamSynchronize(b->leader->stream2);
+    delete b;
+}
+
+int plsa_members_release(plsa_members *b) {
+    if (!b) return fail(nullptr, "plsa_members: NULL batch");
+    plsa_ctx *L = b->leader;
+    HIPCHK(L, hipSetDevice(L->device));
+    HIPCHK(L, hipStreamSynchronize(L->stream));
+    HIPCHK(L, hipStreamSynchronize(L->stream2));
+    for (size_t r = 0; r < b->ctx.size(); ++r) {      // fresh slots: everything a member held goes with its context
+        plsa_members::Member fresh;
+        CHK(new_member(L, fresh));
+        b->ctx[r] = std::move(fresh);
+        b->prepared[r] = 0;
+        b->info[r] = plsa_members::Info{};
+    }
+    return 0;
+}
+
+int plsa_members_prepare(plsa_members *b, int32_t member, const int64_t *idx, int64_t n_out, int32_t k,
+                         uint32_t *mt_state_io, const float *U, const float *V) {
+    CHK(members_check(b, member));
+    plsa_ctx *L = b->leader, *c = b->ctx[member].get();
+    HIPCHK(L, hipSetDevice(L->device));
+    if (L->bn <= 0) return fail(L, "plsa_members_prepare: no corpus uploaded");
+    if (!mt_state_io && (!U || !V)) return fail(L, "plsa_members_prepare: neither a generator state nor host factors");
+    b->prepared[member] = 0;
+    // the base corpus is the leader's (uploaded once): the member views it
+    if (c->bn != L->bn || c->bm != L->bm || c->bnnz != L->bnnz) c->bal_have_frac = false;
+    c->b_indptr.borrow(L->b_indptr.p, L->b_indptr.cap);
+    c->b_col.borrow(L->b_col.p, L->b_col.cap);
+    c->b_val.borrow(L->b_val.p, L->b_val.cap);
+    c->bn = L->bn; c->bm = L->bm; c->bnnz = L->bnnz;
+    ScratchLoan loan(L, c);
+    CHK(member_rc(L, c, plsa_bootstrap(c, idx, n_out)));
+    if (mt_state_io) CHK(member_rc(L, c, mt_init(c, k, mt_state_io, nullptr)));
+    else CHK(member_rc(L, c, plsa_set_factors(c, U, V, c->n, c->m, k)));
+    b->prepared[member] = 1;
+    return 0;
+}
+
+int plsa_members_fit(plsa_members *b, int32_t n_active, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
+                     float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t ll_cap, int32_t *n_ll,
+                     int32_t *n_batched) {
+    if (!b) return fail(nullptr, "plsa_members: NULL batch");
+    plsa_ctx *L = b->leader;
+    HIPCHK(L, hipSetDevice(L->device));
+    if (n_active < 1 || n_active > (int32_t)b->ctx.size()) return fail(L, "plsa_members_fit: n_active=%d outside [1, %d]", n_active, (int)b->ctx.size());
+    if (n_iter < 0 || n_iter_per_test <= 0) return fail(L, "plsa_members_fit: bad n_iter / n_iter_per_test");
+    if (!iters_done || !n_ll) return fail(L, "plsa_members_fit: iters_done / n_ll is NULL");
+    if (ll_trace && ll_cap < n_iter + 2) return fail(L, "plsa_members_fit: ll_cap=%d below n_iter + 2", ll_cap);
+    for (int r = 0; r < n_active; ++r) {
+        if (!b->prepared[r]) return fail(L, "plsa_members_fit: member %d is not prepared", r);
+        if (b->ctx[r]->k != b->ctx[0]->k) return fail(L, "plsa_members_fit: members differ in k");
+        b->info[r] = plsa_members::Info{};
+    }
+    if (n_batched) *n_batched = 0;
+    // what a batch carries: the fused schedule in the engine's own arithmetic, eager, untimed, 32-bit gather tables
+    const bool call_ok = (flags & PLSA_FUSED) && !(flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL | PLSA_SHARDED | PLSA_GRAPH)) &&
+                         !L->ref_sums && !L->ref_ll && !L->graph && !L->timing && !L->row_xcd && n_iter > 0;
+    std::vector<plsa::MemberArgs> args(n_active);
+    std::vector<int> key(n_active, -1);          // instantiation group: packed column stream | packed document stream
+    if (call_ok)
+        for (int r = 0; r < n_active; ++r) {
+            plsa_ctx *c = b->ctx[r].get();
+            if (table_is_wide(c, c->n) || table_is_wide(c, c->m) || c->nnz <= 0) continue;
+            ScratchLoan loan(L, c);
+            CHK(member_rc(L, c, member_args(c, b->ll_out.as<double>(), args[r], b->info[r])));
+            key[r] = (c->packed && c->pk_csc.ok ? 1 : 0) | (c->packed && c->pk_csr.ok ? 2 : 0);
+        }
+    int n_groups = 0, batched = 0;
+    for (int kk = 0; kk < 4; ++kk) {
+        std::vector<int> who;
+        std::vector<plsa::MemberArgs> rows;
+        for (int r = 0; r < n_active; ++r) if (key[r] == kk) who.push_back(r);
+        if (who.size() < 2) continue;
+        for (size_t g = 0; g < who.size(); ++g) {
+            rows.push_back(args[who[g]]);
+            rows.back().ll_out = b->ll_out.as<double>() + g;
+            b->info[who[g]].group = n_groups;
+            b->info[who[g]].group_size = (int)who.size();
+        }
+        CHK(fit_group(b, who, rows, n_iter, n_iter_per_test, tolerance, thresh, flags, iters_done, ll_trace, ll_cap, n_ll));
+        for (int r : who) key[r] = -2;
+        batched += (int)who.size();
+        n_groups++;
+    }
+    for (int r = 0; r < n_active; ++r) {         // the rest: the classic loop, one member after the other
+        if (key[r] == -2) continue;
+        plsa_ctx *c = b->ctx[r].get();
+        ScratchLoan loan(L, c);
+        struct ArithmeticLoan {                  // plsa_set_arithmetic of the leader applies to its members
+            plsa_ctx *c; bool s, l;
+            ArithmeticLoan(plsa_ctx *c_, plsa_ctx *L_) : c(c_), s(c_->ref_sums), l(c_->ref_ll) { c->ref_sums = L_->ref_sums; c->ref_ll = L_->ref_ll; }
+            ~ArithmeticLoan() { c->ref_sums = s; c->ref_ll = l; }
+        } arithmetic(c, L);
+        CHK(member_rc(L, c, plsa_fit(c, nullptr, n_iter, n_iter_per_test, tolerance, thresh, flags, iters_done + r,
+                                     ll_trace ? ll_trace + (size_t)r * ll_cap : nullptr, n_ll + r)));
+        b->last_ll[r] = c->h_ll[0];
+    }
+    if (n_batched) *n_batched = batched;
+    return 0;
+}
+
+int plsa_members_capacity(plsa_ctx *ctx, int32_t k, int32_t *max_members) {
+    if (!ctx || !max_members) return fail(ctx, "plsa_members_capacity: NULL argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->bn <= 0) return fail(ctx, "plsa_members_capacity: no corpus uploaded");
+    if (k <= 0 || k > 1024) return fail(ctx, "plsa_members_capacity: k=%d outside [1,1024]", k);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+    // a member's footprint, from above: resample + row ids + CSC copy + both packed streams (36 bytes per entry, a resample
+    // may hold somewhat more entries than the corpus: 25 % head-room), item partials of both passes at the shortest item
+    // length (16 entries), two sets of factors + the accumulator, and the buffers' own growth margin
+    const double nnz = 1.25 * (double)ctx->bnnz, n = (double)ctx->bn, m = (double)ctx->bm, kp = (k + 3) / 4 * 4;
+    const double per = 1.07 * (36.0 * nnz + 4.0 * kp * ((nnz / 16 + m) + (nnz / 16 + n) + 2 * n + 3 * m) + 64.0 * (n + m)) + (1 << 20);
+    const double fit = 0.5 * (double)free_b / per;                // half of what is free: the stack and the leader's scratch need room too
+    *max_members = (int32_t)std::max(0.0, std::min((double)PLSA_MEMBERS_MAX, fit));
+    return 0;
+}
+
+int plsa_members_copy_components(plsa_members *b, int32_t member, void *dst) {
+    CHK(members_check(b, member));
+    if (!dst) return fail(b->leader, "plsa_members_copy_components: dst is NULL");
+    plsa_ctx *c = b->ctx[member].get();
+    return member_rc(b->leader, c, plsa_copy_components_to_device(c, dst));
+}
+
+int plsa_members_context(plsa_members *b, int32_t member, plsa_ctx **out) {
+    CHK(members_check(b, member));
+    if (!out) return fail(b->leader, "plsa_members_context: out is NULL");
+    *out = b->ctx[member].get();
+    return 0;
+}
+
+int plsa_members_last_ll(plsa_members *b, int32_t member, double *ll) {
+    CHK(members_check(b, member));
+    if (!ll) return fail(b->leader, "plsa_members_last_ll: ll is NULL");
+    *ll = b->last_ll[member];
+    return 0;
+}
+
+int plsa_members_info(plsa_members *b, int32_t member, int32_t *info) {
+    CHK(members_check(b, member));
+    if (!info) return fail(b->leader, "plsa_members_info: info is NULL");
+    const plsa_members::Info &i = b->info[member];
+    const int v[8] = {i.group, i.group_size, i.items, i.rseg, i.n_chunks, i.n_heavy, i.row_grid, i.norm_blocks};
+    for (int j = 0; j < 8; ++j) info[j] = v[j];
+    return 0;
+}
+
+}  // extern "C"

@@ -83,10 +83,14 @@ class Engine:
         # a context is not thread-safe: callers that share the process-wide engine (the reference is
         # driven from dask/joblib thread pools, enstop_.py:209-217) serialise on this lock
         self.lock = threading.RLock()
+        self._member_batch = None      # cached MemberBatch (member_batch): its slots keep their buffers between ensembles
 
     # -- lifetime --------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
+            if getattr(self, "_member_batch", None) is not None:      # the batch borrows this context's streams and corpus
+                self._member_batch.close()
+                self._member_batch = None
             self._L.plsa_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -475,12 +479,31 @@ class Engine:
                     row_wide=bool(wide[0]), col_wide=bool(wide[1]))
 
     def release_scratch(self):
-        """Free the materialised P and other large scratch buffers (re-created on demand)."""
+        """Free the materialised P and other large scratch buffers (re-created on demand), and the buffers of the cached
+        member batch."""
+        if self._member_batch is not None:
+            self._member_batch.release()
         self._ok(self._L.plsa_release_scratch(self._h))
+
+    def member_capacity(self, k):
+        """members of k topics over the resident corpus that fit into half of the free HBM (at most 64)"""
+        out = C.c_int32(0)
+        self._ok(self._L.plsa_members_capacity(self._h, int(k), C.byref(out)))
+        return out.value
+
+    def member_batch(self, n_members):
+        """The engine's cached MemberBatch with at least `n_members` slots (grown by re-creation when too small)."""
+        b = self._member_batch
+        if b is None or b.n_members < n_members:
+            if b is not None:
+                b.close()
+            b = self._member_batch = MemberBatch(self, n_members)
+        return b
 
     # -- measurement ---------------------------------------------------------------------------------
     def timing(self, on=True):
         self._ok(self._L.plsa_timing_enable(self._h, int(on)))
+        self.timing_on = bool(on)
 
     def timing_reset(self):
         self._ok(self._L.plsa_timing_reset(self._h))
@@ -503,6 +526,134 @@ class Engine:
         for line in buf.value.decode().splitlines():
             name, cnt, ms = line.rsplit(" ", 2)
             out[name] = (int(cnt), float(ms))
+        return out
+
+
+class _MemberView(Engine):
+    """A batch member's own context, borrowed from its MemberBatch: the read-only reports and read-backs of Engine
+    (shape, get_factors, pass_info, packed_info, balance_info) apply to it; it is never closed from here."""
+
+    def __init__(self, leader, handle):
+        self._L = leader._L
+        self._h = handle
+        self.device = leader.device
+        self.k = 0
+        self.base_rows = leader.base_rows
+        self.lock = leader.lock
+        self._member_batch = None
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+class MemberBatch:
+    """Up to 64 ensemble members (bootstrap resamples of the corpus resident on `eng`) that advance through the fused EM
+    schedule together, every kernel of an iteration launched once for all of them (include/plsa_hip_members.h, DESIGN.md
+    section 10).  Each member is bit-identical to its standalone fit; the likelihood test is per member.
+
+        batch = MemberBatch(eng, 32)
+        for r in range(32):
+            batch.prepare(r, k, idx=idx_r, rng=rng_r)        # or U=..., V=... (host factors)
+        iters, traces = batch.fit(32, n_iter=50, trace=True)
+        batch.copy_components(r, stack_dst)                  # or batch.components(r)
+    """
+
+    def __init__(self, eng, n_members):
+        if not 1 <= int(n_members) <= _lib.MEMBERS_MAX:
+            raise ValueError("a batch holds 1 to %d members, not %r" % (_lib.MEMBERS_MAX, n_members))
+        self.eng = eng
+        self._L = eng._L
+        self._b = C.c_void_p()
+        self.n_members = int(n_members)
+        self.k = 0
+        self.last_batched = 0
+        eng._ok(self._L.plsa_members_create(eng._h, self.n_members, C.byref(self._b)))
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b.value:
+            if self.eng._h.value:                  # (a batch dies with its engine: Engine.close closes it first)
+                self._L.plsa_members_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def release(self):
+        """free the members' device buffers (the slots stay usable)"""
+        self.eng._ok(self._L.plsa_members_release(self._b))
+
+    def prepare(self, member, k, idx=None, rng=None, U=None, V=None):
+        """member := corpus[idx] (None: the corpus itself) with k topics drawn on the device from `rng` (a legacy
+        RandomState, advanced exactly as plsa_init(random) advances it) or taken from the host factors U [n, k], V [k, m]."""
+        ip = None
+        n_out = 0
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            ip, n_out = idx.ctypes.data, idx.shape[0]
+        if rng is not None:
+            kind, key, pos, has_gauss, cached = rng.get_state()
+            if kind != "MT19937":
+                raise ValueError("not an MT19937 RandomState")
+            state = np.empty(625, np.uint32)
+            state[:624] = key
+            state[624] = pos
+            self.eng._ok(self._L.plsa_members_prepare(self._b, int(member), ip, n_out, int(k), state.ctypes.data, None, None))
+            rng.set_state((kind, state[:624].copy(), int(state[624]), has_gauss, cached))
+        else:
+            U, V = _f32(U), _f32(V)
+            if U.ndim != 2 or V.ndim != 2 or U.shape[1] != int(k) or V.shape[0] != int(k):
+                raise ValueError("host factors must be U [n, k] and V [k, m]")
+            self.eng._ok(self._L.plsa_members_prepare(self._b, int(member), ip, n_out, int(k), None, ptr(U), ptr(V)))
+        self.k = int(k)
+
+    def fit(self, n_active=None, n_iter=100, n_iter_per_test=10, tolerance=0.001, e_step_thresh=1e-32, flags=None, trace=False):
+        """-> (iteration count per member [n_active], list of float32 likelihood traces); `last_batched`: how many of the
+        members went through batched launches (the others through the classic loop: same results)."""
+        n_active = self.n_members if n_active is None else int(n_active)
+        flags = default_flags() if flags is None else int(flags)
+        if trace:
+            flags |= PLSA_TRACE_LL
+        cap = int(n_iter) + 2
+        iters, nll = np.zeros(n_active, np.int32), np.zeros(n_active, np.int32)
+        ll = np.zeros((n_active, cap), np.float32)
+        nb = C.c_int32(0)
+        self.eng._ok(self._L.plsa_members_fit(self._b, n_active, int(n_iter), int(n_iter_per_test), float(tolerance),
+                                              np.float32(e_step_thresh), flags, iters, ll.ctypes.data, cap, nll, C.byref(nb)))
+        self.last_batched = nb.value
+        return iters, [ll[r, :nll[r]].copy() for r in range(n_active)]
+
+    def copy_components(self, member, device_ptr):
+        self.eng._ok(self._L.plsa_members_copy_components(self._b, int(member), int(device_ptr)))
+
+    def member(self, member):
+        """the member's context as a borrowed Engine view (get_factors, shape, pass_info, packed_info, ...)"""
+        h = C.c_void_p()
+        self.eng._ok(self._L.plsa_members_context(self._b, int(member), C.byref(h)))
+        view = _MemberView(self.eng, h)
+        view.k = self.k
+        return view
+
+    def components(self, member):
+        """P(w|z) [k, m] of a member on the host"""
+        return self.member(member).get_factors(want_u=False)[1]
+
+    def last_ll(self, member):
+        """the float64 log-likelihood behind the member's last likelihood test (the traces hold float32, like the reference)"""
+        out = C.c_double(0.0)
+        self.eng._ok(self._L.plsa_members_last_ll(self._b, int(member), C.byref(out)))
+        return out.value
+
+    def info(self, member):
+        """how the member ran in the last fit: launch group (-1: classic loop), members in the group, row items in use and
+        their length, chunk rows of the column pass, heavy columns, document-pass grid, first norm stage's grid"""
+        a = np.zeros(8, np.int32)
+        self.eng._ok(self._L.plsa_members_info(self._b, int(member), a))
+        keys = ("group", "group_size", "row_items", "row_item_entries", "col_chunks", "heavy_columns", "row_grid", "norm_blocks")
+        out = dict(zip(keys, (int(v) for v in a)))
+        out["row_items"] = bool(out["row_items"])
         return out
 
 

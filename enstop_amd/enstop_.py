@@ -26,6 +26,8 @@ from .plsa import _fit_on_engine, _locked
 # single fit saturates the memory system.  Round 4: the member contexts need their own hardware queues (libplsa_hip.so asks
 # for 8 at load time, see include/plsa_hip.h): 7 370-7 520 -> 8 070-8 290 fits/min with four members in flight; six or eight
 # in flight are slower (profiles/r04_hw_queues_api_jobs_6_8.txt), hence the cap (ENSTOP_AMD_CONCURRENT_MEMBERS_MAX: experiments).
+# The GPU-native counterpart of that thread pool is ONE launch chain that carries all members: parallelism="batched"
+# (`_fit_members_batched` below); opt-in, the contexts stay the default.
 CONCURRENT_MEMBERS_MAX = int(os.environ.get("ENSTOP_AMD_CONCURRENT_MEMBERS_MAX", "4"))
 CONCURRENT_MEMBERS_CELLS = float(os.environ.get("ENSTOP_AMD_CONCURRENT_MEMBERS_CELLS", "2e9"))   # nnz * k below which members run concurrently
 
@@ -45,13 +47,101 @@ def concurrent_members(nnz, k, n_jobs):
     return int(min(n_jobs, CONCURRENT_MEMBERS_MAX))
 
 
-last_ensemble_timing = {}      # seconds spent by the last multi-member call of this process (bench.py reports it)
+last_ensemble_timing = {}      # seconds spent by the last multi-member call of this process (bench.py reports it);
+                               # path: "batched" | "contexts", batch: members per launch, groups: launch groups per batch
+
+PARALLELISM = ("dask", "joblib", "none", "batched")
 
 
-def _fit_members(A, k, runs, seeds, member_kw, device, n_jobs, world=1, n_runs=None):
+def _batched_requested(parallelism):
+    """parallelism="batched", or ENSTOP_AMD_ENSEMBLE=batched for the reference's "dask" / "joblib" (A/B measurement through
+    unmodified callers)."""
+    return parallelism == "batched" or (parallelism in ("dask", "joblib") and
+                                        os.environ.get("ENSTOP_AMD_ENSEMBLE", "") == "batched")
+
+
+def batch_members_cap():
+    """ENSTOP_AMD_BATCH_MEMBERS: members per launch (default 32, at most 64)"""
+    from ._lib import MEMBERS_MAX
+    return max(1, min(MEMBERS_MAX, int(os.environ.get("ENSTOP_AMD_BATCH_MEMBERS", "32"))))
+
+
+def _batch_eligible(eng, A, k, member_kw):
+    """What a batch carries: the fused schedule in the engine's own arithmetic, eager and untimed, on a corpus small
+    enough that one fit leaves the GPU idle.  Everything else takes the contexts (same results)."""
+    from ._lib import PLSA_FUSED, PLSA_REFERENCE_LL, PLSA_REFERENCE_SUMS, PLSA_SHARDED
+    from .engine import default_flags
+    PLSA_GRAPH = 128
+    flags = default_flags() if member_kw.get("flags") is None else int(member_kw["flags"])
+    if not flags & PLSA_FUSED or flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL | PLSA_SHARDED | PLSA_GRAPH):
+        return False
+    if os.environ.get("PLSA_GRAPH", "0") not in ("", "0") or getattr(eng, "timing_on", False):
+        return False
+    if A.nnz * float(k) >= CONCURRENT_MEMBERS_CELLS or A.nnz == 0:
+        return False
+    init = member_kw.get("init", "random")
+    if isinstance(init, str) and init == "device_random":
+        return False
+    return member_kw.get("n_iter", 100) > 0
+
+
+def _prepare_member(batch, j, eng, k, bootstrap=True, random_state=None, init="random", **_unused):
+    """`_member_on_engine` + `_fit_on_engine` up to the fit, for slot j of a batch: the bootstrap draw, then the same stream
+    into the initialisation (on the device from the MT19937 state when the factors are large, host plsa_init otherwise)."""
+    from .plsa import plsa_init
+    n_base = eng.base_rows
+    idx = None
+    if bootstrap:
+        rng = check_random_state(random_state)                       # enstop_.py:86
+        idx = rng.randint(0, n_base, size=n_base)                    # enstop_.py:87
+    rng = check_random_state(random_state)
+    n, m = n_base, batch.eng.shape[1]
+    device_init = os.environ.get("ENSTOP_AMD_HOST_INIT", "auto")
+    use_device_init = device_init == "0" or (device_init == "auto" and k * (n + m) >= 262_144)
+    if isinstance(init, str) and init == "random" and isinstance(rng, np.random.RandomState) and use_device_init:
+        batch.prepare(j, k, idx=idx, rng=rng)
+        return
+
+    class _Shape:
+        pass
+    Xs = _Shape()
+    Xs.shape = (n, m)
+    U, V = plsa_init(Xs, k, init=init, rng=rng)
+    batch.prepare(j, k, idx=idx, U=U.astype(np.float32, order="C"), V=V.astype(np.float32, order="C"))
+
+
+def _fit_members_batched(eng, A, k, runs, seeds, member_kw, world, n_runs, B, slots_wanted=0):
+    """The batched branch of `_fit_members`: the runs of this rank in successive batches of at most B members, each batch
+    one launch chain (engine.MemberBatch); run r draws from RandomState(seeds[r]) and lands in slot r // world."""
+    m = A.shape[1]
+    slots = max(1, max((r // world for r in runs), default=0) + 1) if n_runs is None else max(1, (n_runs + world - 1) // world)
+    base = eng.stack_reserve(slots, k, m)
+    batch = eng.member_batch(max(B, slots_wanted))       # (idle slots cost nothing; a later, larger ensemble re-uses them)
+    groups = []
+    for start in range(0, len(runs), B):
+        chunk = runs[start:start + B]
+        for j, r in enumerate(chunk):
+            _prepare_member(batch, j, eng, k, random_state=np.random.RandomState(seeds[r]), **member_kw)
+        batch.fit(len(chunk), member_kw["n_iter"], member_kw["n_iter_per_test"], member_kw["tolerance"],
+                  member_kw["e_step_thresh"], member_kw["flags"])
+        for j, r in enumerate(chunk):
+            batch.copy_components(j, base + 4 * (r // world) * k * m)
+        sizes = {}
+        for j in range(len(chunk)):
+            g = batch.info(j)["group"]
+            sizes[g if g >= 0 else -1 - j] = sizes.get(g if g >= 0 else -1 - j, 0) + 1
+        groups.append(sorted(sizes.values(), reverse=True))
+    last_ensemble_timing.update(groups=groups)
+    return eng
+
+
+def _fit_members(A, k, runs, seeds, member_kw, device, n_jobs, world=1, n_runs=None, batched=0):
     """Fits the given runs of an ensemble on this process' GPU and leaves their topic matrices in the device
     stack of the process-wide engine (run r -> slot r // world); run r draws from RandomState(seeds[r]) whichever
-    engine or thread fits it, so the result does not depend on `n_jobs`.  Returns the engine that holds the stack."""
+    engine or thread fits it, so the result does not depend on `n_jobs`.  Returns the engine that holds the stack.
+    `batched` ((members per launch, slots to keep) or 0: off): the runs go through one launch chain per batch instead of `n_jobs` contexts."""
+    if batched:
+        return _fit_members_batched(get_engine(device), A, k, runs, seeds, member_kw, world, n_runs, batched[0], batched[1])
     jobs = min(concurrent_members(A.nnz, k, n_jobs), max(len(runs), 1))
     engines = get_member_engines(device, jobs)
     for e in engines[1:]:
@@ -166,6 +256,12 @@ def _ensemble_of_plsa_topics(X, k, n_jobs=4, n_runs=16, parallelism="dask", **kw
     `parallelism`:
       "none"            members run serially on this process' GPU sharing `random_state` exactly
                         like the reference's serial branch (enstop_.py:220-223).
+      "batched"         like "dask", but the members of a rank advance through the fused EM schedule TOGETHER: every kernel
+                        of an iteration is launched once for up to ENSTOP_AMD_BATCH_MEMBERS (32) members, each member
+                        bit-identical to its fit under "dask", the likelihood test per member.
+                        Calls a batch cannot carry (reference arithmetic, materialised schedule, nnz * k >= 2e9, ...)
+                        silently take the "dask" path; `last_ensemble_timing["path"]` says which ran.
+                        ENSTOP_AMD_ENSEMBLE=batched sends "dask" / "joblib" this way too (A/B measurement).
       "dask" / "joblib" accepted for drop-in compatibility; the thread fan-out they name is
                         replaced by the one-GPU-per-process model: after
                         `enstop_amd.distributed.init()` under a launcher that sets RANK / WORLD_SIZE
@@ -177,9 +273,8 @@ def _ensemble_of_plsa_topics(X, k, n_jobs=4, n_runs=16, parallelism="dask", **kw
     (reference: every thread re-seeds with the same int, producing identical members,
     enstop_.py:86 -- a documented defect, not reproduced).
     """
-    if parallelism not in ("dask", "joblib", "none"):
-        raise ValueError("Unrecognized parallelism {}; should be one of {}".format(
-            parallelism, ("dask", "joblib", "none")))
+    if parallelism not in PARALLELISM:
+        raise ValueError("Unrecognized parallelism {}; should be one of {}".format(parallelism, PARALLELISM))
     A = X.tocsr() if issparse(X) else csr_matrix(X)
     eng = get_engine(kwargs.get("device", None))
     eng.upload_csr(A)
@@ -213,11 +308,18 @@ def _ensemble_of_plsa_topics(X, k, n_jobs=4, n_runs=16, parallelism="dask", **kw
         out = np.empty((n_runs * k, A.shape[1]), np.float32)
         toucher = threading.Thread(target=out.fill, args=(0.0,), daemon=True)
         toucher.start()
+    batched = 0
+    if _batched_requested(parallelism) and runs and _batch_eligible(eng, A, k, member_kw):
+        room = min(batch_members_cap(), eng.member_capacity(k))
+        batched = min(room, len(runs))
     stack_eng = _fit_members(A, k, runs, {r: base_seed + r for r in runs}, member_kw, kwargs.get("device", None),
-                             n_jobs, world, n_runs)
+                             n_jobs, world, n_runs, (batched, room) if batched else 0)
     t1 = time.perf_counter()
     if toucher is not None:
         toucher.join()
     out = distributed.gather_stack(stack_eng, n_runs, k, A.shape[1], out=out)
-    last_ensemble_timing.update(fit_s=t1 - t0, gather_s=time.perf_counter() - t1, members=len(runs), rank=rank, world=world)
+    last_ensemble_timing.update(fit_s=t1 - t0, gather_s=time.perf_counter() - t1, members=len(runs), rank=rank, world=world,
+                                path="batched" if batched else "contexts", batch=batched if batched else 1)
+    if not batched:
+        last_ensemble_timing.pop("groups", None)
     return out
