@@ -1887,7 +1887,17 @@ __global__ __launch_bounds__(256) void k_hell_finish(const double *__restrict__ 
 // base-2 logarithm) is evaluated while a tile is staged into LDS, the pair term is formed directly
 // (no cancellation between two large dot products), float partial sums are flushed into float64
 // every 256 words.
+// v_log_f32 does not take subnormal inputs (it returns -inf for 0 < p < 2^-126, and one such entry makes
+// a whole D[i, j] non-finite); topic entries that small are reachable (e_step_thresh = 1e-32 over a
+// norm_pwz of 1e5 ... 1e7), so they are scaled into the normal range first.  Normal inputs take the
+// bare instruction as before: their bits do not change.
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float kl_log2(float p) {
+    const bool tiny = p < 1.17549435e-38f;                       // FLT_MIN = 2^-126
+    const float l = __log2f(tiny ? p * 4294967296.f : p);        // 2^32: exact
+    return tiny ? l - 32.f : l;
+}
+
 __global__ __launch_bounds__(256) void k_kl_gram(const float *__restrict__ T, int t, i64 m, i64 slice,
                                                  double *__restrict__ partial /*[slices][t][t]*/) {
     __shared__ float sp[HELL_KSTEP][HELL_TILE + 1], sl[HELL_KSTEP][HELL_TILE + 1];   // row side: p_i, log2 p_i
@@ -1910,8 +1920,8 @@ __global__ __launch_bounds__(256) void k_kl_gram(const float *__restrict__ T, in
             const float pi = (bi + r < t && ww < w1) ? T[(i64)(bi + r) * m + ww] : 0.f;
             const float pj = (bj + r < t && ww < w1) ? T[(i64)(bj + r) * m + ww] : 0.f;
             sp[kk][r] = pi > 0.f ? pi : 0.f;
-            sl[kk][r] = pi > 0.f ? __log2f(pi) : 0.f;
-            sq[kk][r] = pj > 0.f ? __log2f(pj) : 0.f;
+            sl[kk][r] = pi > 0.f ? kl_log2(pi) : 0.f;
+            sq[kk][r] = pj > 0.f ? kl_log2(pj) : 0.f;
             sm[kk][r] = pj > 0.f ? 1.f : 0.f;
         }
         __syncthreads();

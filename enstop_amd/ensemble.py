@@ -19,6 +19,15 @@ no private scikit-learn module is imported.  "hellinger_umap" needs
 `umap-learn` and raises ImportError when it is absent.  The all-pairs Hellinger matrix follows
 umap.distances.hellinger's published definition (umap-learn >= 0.3.8) and is checked against that
 definition, not against a reference run.
+
+The three device kernel families are held ENTRY BY ENTRY to float64 restatements of those statements
+(tests/test_topic_combination.py; u = 2^-24, W = non-zero products of a pair inside one 256-word flush
+window of the kernels): Hellinger `1 - D^2` within (W + 3) u relative, KL within
+(W + 6) u sum p_i (|log2 p_i| + |log2 p_j|), representatives within 6 u relative; symmetry, zero diagonal,
+zero-mass and disjoint-support conventions exact.  Worst observed error / bound on an MI355X: 0.71 / 0.21 /
+0.47 (rows of a dozen non-zeros at the slicing boundaries), 0.0028 / 0.0003 / 0.33 on dense rows at
+t = 640 and 1280 over 173 762 words; inputs include entries below FLT_MIN (`plsa_all_pairs_kl` returned
+non-finite entries for them before that file existed) and t * m above 2^32 elements.
 """
 import numpy as np
 from scipy.sparse import csr_matrix, issparse
