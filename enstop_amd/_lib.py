@@ -1,4 +1,5 @@
-"""ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h and plsa_hip_members.h).
+"""ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h and
+plsa_hip_metrics.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -122,6 +123,11 @@ MEMBER_SIGNATURES = {
     "plsa_members_release": (C.c_int, [_members]),
 }
 
+# include/plsa_hip_metrics.h: topic-quality metrics on the device (its own table, like the members')
+METRIC_SIGNATURES = {
+    "plsa_codocument_counts": (C.c_int, [_ctx, _i32p, _i64, _i32, _i32, _i64p, _i64p]),
+}
+
 _lib = None
 HW_QUEUES = {"set_by": None, "hip_mapped_before_load": None}
 
@@ -171,7 +177,7 @@ def load():
             "(python -m enstop_amd.build). There is no CPU fallback." % LIB_PATH)
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

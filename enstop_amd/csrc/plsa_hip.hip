@@ -32,9 +32,11 @@
 #include "../../include/plsa_hip.h"
 #include "../../include/plsa_hip_diag.h"
 #include "../../include/plsa_hip_members.h"
+#include "../../include/plsa_hip_metrics.h"
 #include "mt_jump.hpp"
 #include "plsa_kernels.hpp"
 #include "plsa_member_kernels.hpp"
+#include "plsa_metric_kernels.hpp"
 #include "plsa_ref_kernels.hpp"
 #include "plsa_synth.hpp"
 
@@ -234,6 +236,9 @@ struct plsa_ctx {
     Pinned<double> h_ll;
 
     DevBuf colsum_rows, colsum_rows2;
+    // plsa_codocument_counts: one 32-bit mask per document and set of a chunk; the chunk's word lists and counters.  Kept
+    // between calls (a sweep scores one model after the other), freed by plsa_release_scratch
+    DevBuf metric_mask, metric_small;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -2988,7 +2993,7 @@ int plsa_release_scratch(plsa_ctx *c) {
                       &c->mt_words, &c->mt_state, &c->mt_fin, &c->mt_poly, &c->mt_seq,
                       // member stack + gather buffers of the ensemble exchange (16 runs x 64 topics x 100 k words = 0.4 GB):
                       // re-created by the next plsa_stack_reserve / plsa_comm_allgather_stack
-                      &c->comm_stack, &c->comm_recv, &c->comm_send})
+                      &c->comm_stack, &c->comm_recv, &c->comm_send, &c->metric_mask, &c->metric_small})
         b->release();
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
@@ -3106,6 +3111,68 @@ int plsa_all_pairs_hellinger(plsa_ctx *c, const float *topics, int64_t t, int64_
     if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, "plsa_all_pairs_hellinger: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// enstop/utils.py:150-203 (the counts behind coherence: pairwise document-list intersections, `data > 0` column sums) on
+// the device: plsa_metric_kernels.hpp
+int plsa_codocument_counts(plsa_ctx *c, const int32_t *words, int64_t sets, int32_t nw, int32_t max_sets_per_pass,
+                           int64_t *co, int64_t *positive) {
+    if (!c) return fail(c, "plsa_codocument_counts: ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nw < 2 || nw > plsa::METRIC_MAX_WORDS)
+        return fail(c, "plsa_codocument_counts: nw=%d outside [2,%d]", nw, plsa::METRIC_MAX_WORDS);
+    if (sets < 1 || sets > ((i64)1 << 24)) return fail(c, "plsa_codocument_counts: sets=%lld outside [1,2^24]", (long long)sets);
+    if (max_sets_per_pass < 0) return fail(c, "plsa_codocument_counts: max_sets_per_pass=%d is negative", max_sets_per_pass);
+    if (!words || !co || !positive) return fail(c, "plsa_codocument_counts: words, co and positive must not be NULL");
+    if (c->n <= 0) return fail(c, "plsa_codocument_counts: no corpus uploaded");
+    // the ids index colptr on the device: checked here, before anything is launched
+    for (i64 i = 0; i < sets * nw; ++i)
+        if (words[i] < 0 || words[i] >= c->m)
+            return fail(c, "plsa_codocument_counts: word id %d (set %lld, position %lld) outside [0,%lld)", words[i],
+                        (long long)(i / nw), (long long)(i % nw), (long long)c->m);
+    const i64 n = c->n, per_co = (i64)nw * nw;
+    std::fill(co, co + sets * per_co, (int64_t)0);
+    std::fill(positive, positive + sets * nw, (int64_t)0);
+    if (c->nnz == 0) return 0;
+    CHK(ensure_csc(c));
+    // sets per pass: a quarter of what is free (the masks already held count as free), at most 4096 (grid z)
+    i64 chunk = max_sets_per_pass;
+    if (chunk == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)1 << 30; }
+        chunk = (i64)((free_b + c->metric_mask.cap) / 4 / (sizeof(unsigned) * (size_t)n));
+    }
+    chunk = std::max<i64>(1, std::min<i64>(std::min<i64>(chunk, sets), 4096));
+    CHK(ensure(c, c->metric_mask, sizeof(unsigned) * (size_t)chunk * (size_t)n));
+    // [chunk][nw][nw] co-document counters, [chunk][nw] positive counters, [chunk][nw] word ids
+    const size_t co_b = sizeof(unsigned long long) * (size_t)(chunk * per_co), pos_b = sizeof(unsigned long long) * (size_t)(chunk * nw);
+    CHK(ensure(c, c->metric_small, co_b + pos_b + sizeof(int) * (size_t)(chunk * nw)));
+    unsigned long long *d_co = c->metric_small.as<unsigned long long>();
+    unsigned long long *d_pos = d_co + chunk * per_co;
+    int *d_words = reinterpret_cast<int *>(d_pos + chunk * nw);
+    // several workgroups per posting list (a head word has about n postings), several per mask row
+    const unsigned mark_x = (unsigned)std::max<i64>(1, std::min<i64>(64, (n + 4095) / 4096));
+    const unsigned count_x = (unsigned)std::max<i64>(1, std::min<i64>(128, (n + 2047) / 2048));
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are copied out as int64");
+    for (i64 s0 = 0; s0 < sets; s0 += chunk) {
+        const i64 cs = std::min<i64>(chunk, sets - s0);
+        HIPCHK(c, hipMemsetAsync(c->metric_mask.p, 0, sizeof(unsigned) * (size_t)cs * (size_t)n, c->stream));
+        HIPCHK(c, hipMemsetAsync(d_co, 0, co_b + pos_b, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_words, words + s0 * nw, sizeof(int) * (size_t)(cs * nw), hipMemcpyHostToDevice, c->stream));
+        { Scope s(c, "k_metric_mark");
+          hipLaunchKernelGGL(plsa::k_metric_mark, dim3(mark_x, (unsigned)nw, (unsigned)cs), dim3(plsa::METRIC_BLOCK), 0, c->stream,
+                             c->csc.colptr.as<int>(), c->csc.row.as<int>(), c->csc.val.as<float>(), d_words, (int)nw, (int64_t)n,
+                             c->metric_mask.as<unsigned>(), d_pos); }
+        CHK(launch_check(c, "k_metric_mark"));
+        { Scope s(c, "k_metric_count");
+          hipLaunchKernelGGL(plsa::k_metric_count, dim3(count_x, (unsigned)cs), dim3(plsa::METRIC_BLOCK), 0, c->stream,
+                             c->metric_mask.as<unsigned>(), (int)nw, (int64_t)n, d_co); }
+        CHK(launch_check(c, "k_metric_count"));
+        HIPCHK(c, hipMemcpyAsync(co + s0 * per_co, d_co, sizeof(int64_t) * (size_t)(cs * per_co), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(positive + s0 * nw, d_pos, sizeof(int64_t) * (size_t)(cs * nw), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // the next chunk reuses the staging buffers
+    }
     return 0;
 }
 

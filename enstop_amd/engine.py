@@ -441,6 +441,21 @@ class Engine:
         self._ok(self._L.plsa_cluster_representatives(self._h, ptr(T), t, m, lab, ptr(w), n_clusters, out))
         return out
 
+    def codocument_counts(self, words, max_sets_per_pass=0):
+        """Co-document counts of word lists on the ACTIVE matrix (include/plsa_hip_metrics.h; enstop/utils.py:150-203).
+        words: int [sets, nw], 2 <= nw <= 32, distinct ids per row.  -> (co [sets, nw, nw] int64: documents with a stored
+        entry in both columns, the diagonal the column's stored entries; positive [sets, nw] int64: entries > 0).  Exact.
+        max_sets_per_pass: cap of the sets whose document masks are held at once (0: chosen from the free memory)."""
+        W = np.ascontiguousarray(words, dtype=np.int32)
+        if W.ndim != 2:
+            raise ValueError("words must be a 2-D array [sets, nw]")
+        sets, nw = W.shape
+        co = np.zeros((sets, nw, nw), np.int64)
+        positive = np.zeros((sets, nw), np.int64)
+        self._ok(self._L.plsa_codocument_counts(self._h, W.reshape(-1), sets, nw, int(max_sets_per_pass), co.reshape(-1),
+                                                positive.reshape(-1)))
+        return co, positive
+
     def reference_chain_info(self):
         """norm_pwz of the reference arithmetic (plsa_reference_chain_info): chunks of the parity-pair walk that took the slow way,
         chunks walked, and whether this context is on the serial chain for the current corpus."""

@@ -1,9 +1,12 @@
-"""Host-side helpers with the reference's names (enstop/utils.py): input standardisation and
-sample-weight validation used by the estimators.  Not hot-path code."""
+"""Helpers with the reference's names (enstop/utils.py): input standardisation and sample-weight validation used by the
+estimators (host-side, not hot-path code), and the topic-quality metrics -- coherence counts on the device when one is
+there (plsa_codocument_counts), everything else on the host."""
+import os
+
 import numpy as np
 from sklearn.preprocessing import normalize as _sk_normalize
 
-from .engine import host_normalize_rows
+from .engine import get_engine, host_normalize_rows
 
 
 def normalize(ndarray, axis=0):
@@ -52,7 +55,7 @@ except ImportError:          # a private name: keep working if a scikit-learn re
 
 
 # ------------------------------------------------------------------------------------------------
-# topic-quality metrics (enstop/utils.py:44-273): host-side NumPy, not hot-path code
+# topic-quality metrics (enstop/utils.py:44-273): log-lift in host NumPy; the counts behind coherence on the device or the host
 # ------------------------------------------------------------------------------------------------
 def _empirical_probs(data):
     p = np.asarray(data.sum(axis=0)).squeeze().astype(np.float64)
@@ -80,17 +83,32 @@ def mean_log_lift(topics, data, n_words=-1):
     return np.mean([_log_lift(np.asarray(topics), z, e, n_words) for z in range(np.asarray(topics).shape[0])])
 
 
-def _coherence(topics, z, n, B, n_docs_per_word):
-    top = np.argsort(topics[z])[-n:]
-    sub = B[:, top]
-    co = np.asarray((sub.T @ sub).todense(), dtype=np.float64)        # co-document counts of the top words
+def _coherence_from_counts(co, positive):
+    """Coherence of one word list from its counts (the sum of enstop/utils.py:186-197): co [nw, nw] co-document counts of
+    the list's words in their order, positive [nw] documents in which each word has a positive count.  Both back-ends
+    finish here, so they return the same float64 bits."""
+    co = np.asarray(co, dtype=np.float64)
+    n = co.shape[0]
     total = 0.0
     for i in range(n - 1):
-        w = top[i]
-        if n_docs_per_word[w] == 0:
+        if positive[i] == 0:
             continue
-        total += np.sum(np.log((co[i, i + 1:] + 1.0) / n_docs_per_word[w]))
+        total += np.sum(np.log((co[i, i + 1:] + 1.0) / positive[i]))
     return total
+
+
+def _top_words(topics, z, n):
+    return np.argsort(topics[z])[-n:]       # ascending: word i of the list is the denominator of every pair (i, j > i)
+
+
+def _host_counts(top, B, n_docs_per_word):
+    sub = B[:, top]
+    co = np.asarray((sub.T @ sub).todense(), dtype=np.float64)        # co-document counts of the top words
+    return co, n_docs_per_word[top]
+
+
+def _coherence(topics, z, n, B, n_docs_per_word):
+    return _coherence_from_counts(*_host_counts(_top_words(topics, z, n), B, n_docs_per_word))
 
 
 def _binarised(data):
@@ -102,13 +120,103 @@ def _binarised(data):
     return B, n_docs
 
 
-def coherence(topics, z, data, n_words=20):
-    """UMass-style coherence of topic z over its top `n_words` words (enstop/utils.py:155-197)."""
-    B, n_docs = _binarised(data)
-    return _coherence(np.asarray(topics), z, n_words, B, n_docs)
+# -- back-end of the coherence counts ---------------------------------------------------------------------------------
+METRIC_BACKENDS = ("host", "device", "auto")
+DEVICE_MAX_WORDS = 32        # bits of a document mask (plsa_metric_kernels.hpp)
+last_metric_path = None      # "device" / "host": where the counts of the last coherence / mean_coherence call were taken
+_device_seen = None
 
 
-def mean_coherence(topics, data, n_words=20):
-    B, n_docs = _binarised(data)
+def _device_present():
+    """True when the library loads and the process-wide engine can be had (cached once it could)."""
+    global _device_seen
+    if _device_seen is None:
+        try:
+            get_engine()
+            _device_seen = True
+        except (ImportError, OSError, RuntimeError, AttributeError):
+            return False          # not cached: a library built later in the process is found
+    return _device_seen
+
+
+def _requested_backend(backend):
+    if backend is None:
+        backend = (os.environ.get("ENSTOP_AMD_METRICS") or "auto").strip().lower()
+        if backend not in METRIC_BACKENDS:
+            raise ValueError("ENSTOP_AMD_METRICS=%r: expected one of %s" % (backend, ", ".join(METRIC_BACKENDS)))
+        return backend, False
+    if backend not in ("host", "device"):
+        raise ValueError('backend must be None, "host" or "device", not %r' % (backend,))
+    return backend, backend == "device"
+
+
+def _device_obstacle(topics, data, n_words):
+    """Why the device cannot take this call (None: it can)."""
+    from scipy.sparse import issparse
+    if not 2 <= n_words <= DEVICE_MAX_WORDS:
+        return "n_words=%r outside [2, %d]" % (n_words, DEVICE_MAX_WORDS)
+    if not issparse(data):
+        return "dense data"
+    if data.format not in ("csr", "csc") or not data.has_canonical_format:
+        return "a sparse matrix that is not in canonical CSR / CSC format (duplicate or unsorted entries)"
+    n, m = data.shape
+    if topics.ndim != 2 or topics.shape[0] < 1 or topics.shape[1] != m or n_words > m:
+        return "topics that do not match the data (or fewer than n_words words)"
+    if n < 1 or data.nnz > 2 ** 31 - 64 or max(n, m) >= 2 ** 31 - 1:
+        return "a matrix outside the device's 32-bit index range"
+    return None
+
+
+def _use_device(topics, data, n_words, backend):
+    backend, explicit = _requested_backend(backend)
+    if backend == "host" or n_words == 1:          # (one word: no pairs, 0.0 on either path)
+        return False
+    why = _device_obstacle(topics, data, n_words)
+    if why is not None:
+        if explicit:
+            raise ValueError('backend="device" cannot score ' + why)
+        return False
+    return True if backend == "device" else _device_present()
+
+
+def _device_counts(words, data):
+    """(co [sets, nw, nw], positive [sets, nw]) of the word lists on `data`, counted on the device: the engine lock of the
+    fit functions, one upload of the corpus' pattern, one call."""
+    from scipy.sparse import csr_matrix
+    X = data.tocsr()
+    # the values travel as (value > 0): a cast of the real ones to float32 could flush a tiny positive float64 to zero
+    pattern = csr_matrix(((X.data > 0).astype(np.float32), X.indices, X.indptr), shape=X.shape)
+    eng = get_engine()
+    with eng.lock:
+        eng.upload_csr(pattern)
+        return eng.codocument_counts(words)
+
+
+def coherence(topics, z, data, n_words=20, backend=None):
+    """UMass-style coherence of topic z over its top `n_words` words (enstop/utils.py:155-197).
+    backend: "host" (NumPy / SciPy), "device" (the counts on the GPU: sparse canonical data, 2 <= n_words <= 32, else
+    ValueError) or None: ENSTOP_AMD_METRICS = host | device | auto (default auto: the device when there is one and it can
+    carry the call).  Both give the same float64 bits; `last_metric_path` says which ran."""
+    global last_metric_path
     topics = np.asarray(topics)
+    if _use_device(topics, data, n_words, backend):
+        co, positive = _device_counts(_top_words(topics, z, n_words)[None, :], data)
+        last_metric_path = "device"
+        return _coherence_from_counts(co[0], positive[0])
+    B, n_docs = _binarised(data)
+    last_metric_path = "host"
+    return _coherence(topics, z, n_words, B, n_docs)
+
+
+def mean_coherence(topics, data, n_words=20, backend=None):
+    """Mean of coherence() over the topics; on the device all topics' lists go through one call."""
+    global last_metric_path
+    topics = np.asarray(topics)
+    if _use_device(topics, data, n_words, backend):
+        words = np.stack([_top_words(topics, z, n_words) for z in range(topics.shape[0])])
+        co, positive = _device_counts(words, data)
+        last_metric_path = "device"
+        return np.mean([_coherence_from_counts(co[z], positive[z]) for z in range(topics.shape[0])])
+    B, n_docs = _binarised(data)
+    last_metric_path = "host"
     return np.mean([_coherence(topics, z, n_words, B, n_docs) for z in range(topics.shape[0])])
