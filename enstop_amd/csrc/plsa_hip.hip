@@ -147,6 +147,7 @@ struct plsa_ctx {
         i64 n_items = 0;
     } csc;
     int seg_override = 0, struct_lpn = 0;   // column item length: adaptive unless PLSA_COL_SEG is set
+    int struct_row_lpn = 0;          // document-pass lane count the row items were sized for (struct_lpn: the column pass')
     DevBuf partial;
     bool use_item_order = true, xcd_split = true;
     // packed entry streams of the fused passes (plsa_kernels.hpp: Packed): pk_csr parallel to col / val, pk_csc parallel to
@@ -953,7 +954,7 @@ int upload_sw(plsa_ctx *c, const float *sw, const float **d_sw) {
 void set_shape(plsa_ctx *c, int k) {
     const int kp = (k + 3) / 4 * 4;
     c->k = k; c->kp = kp;
-    const int prev_lpn = c->struct_lpn;
+    const int prev_lpn = c->struct_lpn, prev_row_lpn = c->struct_row_lpn;
     int lpn = 1;
     while (lpn < kp / 4 && lpn < 64) lpn *= 2;
     // k >= 128: 8 floats per lane (two float4 chunks) -- fewer reduction/shuffle instructions per
@@ -967,8 +968,13 @@ void set_shape(plsa_ctx *c, int k) {
     // config 3, while the column pass is 3.5 % SLOWER in that shape (32 items per chunk) and keeps 16 x 1
     c->row_lpn = c->lpn; c->row_ch = c->ch;
     if (c->row_shape_8x2 && c->lpn == 16 && c->ch == 1 && kp == 64) { c->row_lpn = 8; c->row_ch = 2; }
-    if (lpn != prev_lpn) {        // item lengths / the row-item decision depend on the lane shape
+    // the row-item decision and length follow the DOCUMENT pass' lane count (ensure_ritems), which changes between
+    // kp = 60 and kp = 64 while lpn stays 16: watched on its own
+    if (c->row_lpn != prev_row_lpn) {
         c->ritems.invalidate();
+        c->struct_row_lpn = c->row_lpn;
+    }
+    if (lpn != prev_lpn) {        // column item lengths depend on the lane shape
         c->eitems.invalidate();
         if (!c->seg_override) c->csc.invalidate();
         c->struct_lpn = lpn;
