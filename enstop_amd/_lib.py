@@ -18,6 +18,7 @@ PLSA_TRACE_LL = 4
 PLSA_SW_LL_ONLY = 8
 PLSA_STOP_NO_ZERO_ARM = 16
 PLSA_SHARDED = 64
+PLSA_GRAPH = 128            # plsa_fit (fused): the iterations between two likelihood tests replayed from a hipGraph
 PLSA_REFERENCE_SUMS = 256   # the reference's float32 sums, rounding for rounding (include/plsa_hip.h)
 PLSA_REFERENCE_LL = 512     # + the log-likelihood as one sequential float32 sum (plsa.py:322 read literally)
 
@@ -88,6 +89,7 @@ SIGNATURES = {
                                      C.POINTER(C.c_int64)]),
     "plsa_packed_info": (C.c_int, [_ctx, C.POINTER(_i32), C.POINTER(_i32)]),
     "plsa_pass_info": (C.c_int, [_ctx, _i32p, _i32p, _i32p]),
+    "plsa_fit_info": (C.c_int, [_ctx, _i32p]),
     "plsa_release_scratch": (C.c_int, [_ctx]),
     "plsa_timing_enable": (C.c_int, [_ctx, _i32]),
     "plsa_timing_reset": (C.c_int, [_ctx]),

@@ -253,6 +253,13 @@ struct plsa_ctx {
     double bal_end_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per-XCD finish times of the last timed launch
     int small_grid = 0;              // PLSA_SMALL_GRID: workgroups per CU of the column pass on small corpora (0 = no cap)
     int colsum_rows_used = 0;        // rows of colsum_rows written by the last column pass
+    // plsa_fit_info: how the last plsa_fit / plsa_refit ran (written where the decisions are made, read by tests only)
+    struct FitInfo {
+        int fused = 0, pipelined = 0, speculated = 0, graph_launches = 0;
+        int tail = 0;                // column tail: 0 none ran, 1 the single sweep (k_col_reduce_norm), 2 the four-kernel form
+        int two_stage = 0;           // norm_pwz went through k_norm_reduce
+        int xcd_split = 0;           // the last column pass walked its chunks in per-XCD stretches
+    } fit_info;
 
     // multi-GPU exchange: one RCCL communicator per context (one process per GPU), collectives are
     // enqueued on the context's own streams
@@ -1256,6 +1263,7 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
         const bool u_fits_l2 = (double)c->n * c->kp * 4.0 <= 2.0 * 1024 * 1024;
         const int xcd_split = (c->xcd_split && n_chunks >= 64 && !u_fits_l2) ? 1 : 0;
         if (parts & 1) {
+            c->fit_info.xcd_split = xcd_split;
             rc = ensure(c, c->colsum_rows, sizeof(double) * (size_t)std::max(n_chunks, 1) * c->kp);
             if (rc) return;
             const size_t smem = sizeof(double) * (size_t)GPB * c->kp;
@@ -1351,9 +1359,13 @@ int run_v_normalise(plsa_ctx *c) {
 // four-kernel form (k_col_reduce, k_colsum_partial, k_colsum_final, k_v_normalise).
 int run_col_tail(plsa_ctx *c) {
     if (c->sharded) {
+        c->fit_info.tail = 2;
+        c->fit_info.two_stage = 0;
         CHK(run_col_pass(c, false, nullptr, 0.f, 2));
         return run_v_normalise(c);
     }
+    c->fit_info.tail = 1;
+    c->fit_info.two_stage = c->colsum_rows_used > 2048;
     const int rows = c->colsum_rows_used;
     if (rows <= 0) return fail(c, "internal: column tail without a column pass");
     CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
@@ -2320,6 +2332,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
     HIPCHK(c, hipSetDevice(c->device));
     CHK(need_factors(c));
     if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_fit: bad n_iter / n_iter_per_test");
+    c->fit_info = plsa_ctx::FitInfo{};
     ArithmeticScope arithmetic_scope(c, flags);
     if ((c->ref_sums || c->ref_ll) && (flags & PLSA_SHARDED))
         return fail(c, "plsa_fit: PLSA_REFERENCE_SUMS / PLSA_REFERENCE_LL have no doc-sharded form (the reference's sums are single chains over all non-zeros)");
@@ -2327,6 +2340,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
     // one such arithmetic, so PLSA_FUSED has nothing to select there and is ignored
     const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll, trace = flags & PLSA_TRACE_LL;
     const bool zero_arm = !(flags & PLSA_STOP_NO_ZERO_ARM);
+    c->fit_info.fused = fused;
     struct ShardedScope {           // PLSA_SHARDED: this context's rows are one shard of the corpus
         plsa_ctx *c;
         ShardedScope(plsa_ctx *c_, bool on) : c(c_) { c->sharded = on; }
@@ -2373,6 +2387,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
         // small corpora: column chain and document pass as two pipelines that exchange events (see below)
         const bool pipelined = c->overlap && !c->sharded && !graph_requested && c->pipeline &&
                                (double)c->nnz * c->kp < c->overlap_full_limit;
+        c->fit_info.pipelined = pipelined;
         if (pipelined) {      // everything enqueued so far (factors, corpus) precedes both pipelines
             HIPCHK(c, hipEventRecord(c->ev_row, c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_row, 0));
@@ -2399,6 +2414,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                 if (c->cv == 2) { std::swap(c->Vt[2], c->Vt[0]); c->cv = 0; }
             }
         } rot3_scope{c};
+        c->fit_info.speculated = speculate;
         if (speculate) {
             CHK(ensure(c, c->U[2], sizeof(float) * (size_t)c->n * c->kp));
             CHK(ensure(c, c->Vt[2], sizeof(float) * (size_t)c->m * c->kp));
@@ -2515,6 +2531,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
                     HIPCHK(c, e_inst);
                 }
                 HIPCHK(c, hipGraphLaunch(gexec, c->stream));
+                c->fit_info.graph_launches++;
                 iters += 2;
                 ++i;
                 pending = (i % n_iter_per_test == 0);
@@ -2587,8 +2604,10 @@ int plsa_refit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_
     HIPCHK(c, hipSetDevice(c->device));
     CHK(need_factors(c));
     if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_refit: bad n_iter / n_iter_per_test");
+    c->fit_info = plsa_ctx::FitInfo{};
     ArithmeticScope arithmetic_scope(c, flags);
     const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll, trace = flags & PLSA_TRACE_LL;
+    c->fit_info.fused = fused;
     const float *d_sw = nullptr;
     CHK(upload_sw(c, sw, &d_sw));
     int nll = 0, iters = 0;
@@ -2979,6 +2998,14 @@ int plsa_pass_info(plsa_ctx *c, int32_t *col, int32_t *row, int32_t *wide) {
     if (row) { row[0] = c->row_lpn; row[1] = c->row_ch; row[2] = c->kp == 4 * c->row_lpn * c->row_ch; }
     // the tables each fused pass gathers from (dispatch_shape_row, run_col_pass): P(w|z), m rows; P(z|d), n rows
     if (wide) { wide[0] = table_is_wide(c, c->m); wide[1] = table_is_wide(c, c->n); }
+    return 0;
+}
+
+int plsa_fit_info(plsa_ctx *c, int32_t *info) {
+    if (!info) return fail(c, "plsa_fit_info: NULL argument");
+    const plsa_ctx::FitInfo &f = c->fit_info;
+    info[0] = f.fused; info[1] = f.pipelined; info[2] = f.speculated; info[3] = f.graph_launches;
+    info[4] = f.tail; info[5] = f.two_stage; info[6] = f.xcd_split;
     return 0;
 }
 

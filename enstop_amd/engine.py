@@ -493,6 +493,17 @@ class Engine:
         return dict(col=(int(col[0]), int(col[1]), bool(col[2])), row=(int(row[0]), int(row[1]), bool(row[2])),
                     row_wide=bool(wide[0]), col_wide=bool(wide[1]))
 
+    def fit_info(self):
+        """How the last fit / refit on this engine ran: fused loop, pipelined (two event-linked streams), speculated (an
+        iteration enqueued ahead of an unread likelihood test), hipGraph launches, column tail ('sweep': k_col_reduce_norm,
+        'four_kernels': the doc-sharded form, None: none ran), two-stage norm_pwz, XCD split of the last column pass.  The
+        last three are written by the column pass and its tail, so after m_step they describe that call's."""
+        a = np.zeros(7, np.int32)
+        self._ok(self._L.plsa_fit_info(self._h, a))
+        return dict(fused=bool(a[0]), pipelined=bool(a[1]), speculated=bool(a[2]), graph_launches=int(a[3]),
+                    col_tail={0: None, 1: "sweep", 2: "four_kernels"}[int(a[4])], two_stage_norm=bool(a[5]),
+                    xcd_split=bool(a[6]))
+
     def release_scratch(self):
         """Free the materialised P and other large scratch buffers (re-created on demand), and the buffers of the cached
         member batch."""

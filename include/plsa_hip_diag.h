@@ -89,6 +89,14 @@ int plsa_packed_info(plsa_ctx *ctx, int32_t *csr, int32_t *csc);
  * Any pointer may be NULL; fails before plsa_set_factors. */
 int plsa_pass_info(plsa_ctx *ctx, int32_t *col /*[3]*/, int32_t *row /*[3]*/, int32_t *wide /*[2]*/);
 
+/* How the last plsa_fit / plsa_refit on this context ran, for tests that must know which loop and which column tail they
+ * reached.  info = {fused loop, pipelined (column chain and document pass on two event-linked streams), speculated (the third
+ * buffer set: an iteration enqueued ahead of an unread likelihood test), hipGraph launches, column tail (0 none ran, 1 the
+ * single sweep k_col_reduce_norm, 2 the four-kernel form of the doc-sharded fit), two-stage norm_pwz (k_norm_reduce ran),
+ * XCD split of the last column pass}.  A fit resets all seven when it starts; the last three are written by the column
+ * pass and its tail themselves, so after plsa_m_step they describe that call's.  Changes no behaviour. */
+int plsa_fit_info(plsa_ctx *ctx, int32_t *info /*[7]*/);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * HIP events on the context's own stream around every kernel launch (bench.py roofline figures).  */
 int plsa_timing_enable(plsa_ctx *ctx, int32_t on);
