@@ -130,6 +130,12 @@ METRIC_SIGNATURES = {
     "plsa_codocument_counts": (C.c_int, [_ctx, _i32p, _i64, _i32, _i32, _i64p, _i64p]),
 }
 
+# include/plsa_hip_blocked.h: the reference arithmetic under a P(z|w,d) budget (memory plumbing, its own table as well)
+BLOCKED_SIGNATURES = {
+    "plsa_set_p_budget": (C.c_int, [_ctx, _i64]),
+    "plsa_p_block_info": (C.c_int, [_ctx, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)]),
+}
+
 _lib = None
 HW_QUEUES = {"set_by": None, "hip_mapped_before_load": None}
 
@@ -179,7 +185,8 @@ def load():
             "(python -m enstop_amd.build). There is no CPU fallback." % LIB_PATH)
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
+            list(BLOCKED_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -9,7 +9,8 @@ DEPS = [SRC, os.path.join(HERE, "csrc", "plsa_kernels.hpp"), os.path.join(HERE, 
         os.path.join(HERE, "csrc", "plsa_members.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_members.h"), os.path.join(HERE, "csrc", "plsa_ref_kernels.hpp"),
         os.path.join(HERE, "csrc", "plsa_synth.hpp"), os.path.join(HERE, "csrc", "mt_jump.hpp"),
         os.path.join(os.path.dirname(HERE), "include", "plsa_hip.h"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_diag.h"),
-        os.path.join(HERE, "csrc", "plsa_metric_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_metrics.h")]
+        os.path.join(HERE, "csrc", "plsa_metric_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_metrics.h"),
+        os.path.join(os.path.dirname(HERE), "include", "plsa_hip_blocked.h")]
 OUT = os.path.join(HERE, "libplsa_hip.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))

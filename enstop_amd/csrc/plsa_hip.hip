@@ -33,6 +33,7 @@
 #include "../../include/plsa_hip_diag.h"
 #include "../../include/plsa_hip_members.h"
 #include "../../include/plsa_hip_metrics.h"
+#include "../../include/plsa_hip_blocked.h"
 #include "mt_jump.hpp"
 #include "plsa_kernels.hpp"
 #include "plsa_member_kernels.hpp"
@@ -220,6 +221,17 @@ struct plsa_ctx {
     const float *ref_e_sw = nullptr; // weights the next E-step should form its tile sums with
     bool ref_e_no_sums = false;      // the E-steps of a refit: no norm_pwz chain follows
     struct RefHeavy : Derived<RefHeavy> { DevBuf cols; int n = 0, min = 0; } ref_heavy;   // the reference arithmetic's long columns: [count, columns...]
+    // plsa_set_p_budget: the drivers' reference arithmetic with P(z|w,d) of one block of documents at a time.  The plan cuts the
+    // ACTIVE matrix' documents greedily into blocks [doc[b], doc[b + 1]) = entries [ent[b], ent[b + 1]) that fit the budget.
+    int64_t p_budget = 0;          // bytes; 0: none (P holds all non-zeros)
+    struct RefBlocks : Derived<RefBlocks> {
+        std::vector<i64> doc, ent;
+        int64_t budget = 0;        // the budget and the padded topic count the plan was made for
+        int kp = 0;
+        i64 largest = 0;           // non-zeros of the largest block
+        int blocks() const { return (int)doc.size() - 1; }
+    } ref_blocks;
+    struct PBlockInfo { int64_t budget = 0; int blocks = 0; int64_t largest = 0, p_bytes = 0; } p_block_info;   // last driver iteration
     Pinned<unsigned long long> h_ref_stats;   // [2]: chunks that took the slow way / chunks, of the last finished walk
     Event ev_ref_stats;
     bool ref_stats_pending = false;
@@ -632,6 +644,7 @@ void set_active_pointers(plsa_ctx *c) {
     }
     c->rowidx.invalidate(); c->csc.invalidate(); c->pk_csr.invalidate(); c->pk_csc.invalidate(); c->roworder.invalidate();
     c->ritems.invalidate(); c->eitems.invalidate(); c->p_state.invalidate(); c->ref_heavy.invalidate(); c->ref_tsum.invalidate();
+    c->ref_blocks.invalidate();
     c->ref_pairs_off = false;
 }
 
@@ -1001,26 +1014,34 @@ int need_factors(plsa_ctx *c) {
 // ---------------------------------------------------------------------------------------------
 // kernel wrappers
 // ---------------------------------------------------------------------------------------------
-int run_ref_e_step(plsa_ctx *c, float thresh);
-int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw);
+// a block of documents of the budgeted reference arithmetic: entries [e0, e0 + nnz) of the COO order, documents [d0, d1)
+struct RefSpan {
+    i64 e0, nnz;
+    int d0, d1;
+    i64 cap;           // non-zeros of the plan's largest block: scratch is sized once for all blocks
+    bool first, last;
+};
+int run_ref_e_step(plsa_ctx *c, float thresh, const RefSpan *span = nullptr);
+int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw, const RefSpan *span = nullptr);
 int ensure_ref_heavy(plsa_ctx *c);
 bool ref_pairs_now(const plsa_ctx *c);
 int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz);
 int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out);
 
-int run_e_step(plsa_ctx *c, float thresh) {
-    c->ref_tsum.invalidate();          // (a new P(z|w,d): the tile sums of the last reference-arithmetic E-step are history)
+// P(z|w,d) for `rows` non-zeros (all of them, or the largest block of a budgeted reference-arithmetic iteration)
+int ensure_p(plsa_ctx *c, i64 rows) {
     {   // the materialised schedule needs the whole nnz x kp array: say so instead of a bare OOM
-        const size_t need = sizeof(float) * (size_t)(c->nnz + 64) * (size_t)c->kp;
+        const size_t need = sizeof(float) * (size_t)(rows + 64) * (size_t)c->kp;
         size_t free_b = 0, total_b = 0;
         if (!c->P.borrowed && c->P.cap < need && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + c->P.cap < need)
             return fail(c, c->ref_sums ? "the reference arithmetic (PLSA_REFERENCE_SUMS) stores P(z|w,d) like the reference does: %.1f GB needed, "
-                                         "%.1f GB of HBM free -- at this size only the default arithmetic is available"
+                                         "%.1f GB of HBM free -- at this size only the default arithmetic is available, or this one block "
+                                         "of documents at a time (plsa_set_p_budget / p_budget=, plsa_fit and plsa_refit)"
                                        : "materialising P(z|w,d) needs %.1f GB but only %.1f GB of HBM are free; use the fused "
                            "schedule (PLSA_FUSED), which never stores it, or tile the documents (plsa_em_accumulate_materialised)", need / 1e9, (free_b + c->P.cap) / 1e9);
     }
     if (c->P.borrowed || c->p_lent) {
-        const size_t need = sizeof(float) * (size_t)(c->nnz + 64) * (size_t)c->kp;
+        const size_t need = sizeof(float) * (size_t)(rows + 64) * (size_t)c->kp;
         if (c->P.cap < need)
             return fail(c, c->P.borrowed ? "the borrowed P(z|w,d) buffer holds %.2f GB, this matrix needs %.2f GB (plsa_p_borrow)"
                                          : "the P(z|w,d) buffer lent out by plsa_p_reserve holds %.2f GB, this matrix needs %.2f GB: it cannot "
@@ -1031,11 +1052,19 @@ int run_e_step(plsa_ctx *c, float thresh) {
     // one tile (64 rows) of slack: the last tile is stored without a predicate
     {   // placement experiment knobs: PLSA_P_SLACK_MB over-allocates, PLSA_P_OFFSET_KB shifts the start
         const char *s1 = getenv("PLSA_P_SLACK_MB"), *s2 = getenv("PLSA_P_OFFSET_KB");
-        const size_t slack = s1 ? (size_t)atoll(s1) << 20 : 0;
-        c->p_shift = s2 ? (size_t)atoll(s2) * 1024 : 0;
-        CHK(ensure_best_placement(c, c->P, sizeof(float) * (size_t)(c->nnz + 64) * (size_t)c->kp + std::max(slack, c->p_shift),
-                                  c->placement_candidates, c->placement_gbps, &c->placement_tried));
+        // (under a budget: neither knob, and no placement candidates -- they are held side by side while they are compared)
+        const bool budgeted = c->ref_sums && c->p_budget > 0;
+        const size_t slack = s1 && !budgeted ? (size_t)atoll(s1) << 20 : 0;
+        c->p_shift = s2 && !budgeted ? (size_t)atoll(s2) * 1024 : 0;
+        CHK(ensure_best_placement(c, c->P, sizeof(float) * (size_t)(rows + 64) * (size_t)c->kp + std::max(slack, c->p_shift),
+                                  budgeted ? 1 : c->placement_candidates, c->placement_gbps, &c->placement_tried));
     }
+    return 0;
+}
+
+int run_e_step(plsa_ctx *c, float thresh) {
+    c->ref_tsum.invalidate();          // (a new P(z|w,d): the tile sums of the last reference-arithmetic E-step are history)
+    CHK(ensure_p(c, c->nnz));
     // Two traversals.  Document-owned: a group keeps its document's P(z|d) row in registers and gathers only
     // P(w|z) rows (config 3 5.3 ms against 6.3 ms for one group per non-zero), and with the documents cut
     // into pieces of 4 index batches every group of a wave runs the same number of gather/store bursts
@@ -1472,11 +1501,15 @@ int dispatch_ref_group(plsa_ctx *c, Fn &&fn) {
     return 0;
 }
 
-// plsa.py:91-105 with one float32 norm per entry, topics in order (P allocated by run_e_step)
-int run_ref_e_step(plsa_ctx *c, float thresh) {
+// plsa.py:91-105 with one float32 norm per entry, topics in order (P allocated by run_e_step); span: the entries of one block of
+// documents into the block's P (allocated by run_ref_em_blocked)
+int run_ref_e_step(plsa_ctx *c, float thresh, const RefSpan *span) {
     CHK(ensure_rowidx(c));
+    const i64 e0 = span ? span->e0 : 0, nnz = span ? span->nnz : c->nnz;
+    const int *ri = c->rowidx.ids.as<int>() + e0, *ci = c->col + e0;
+    const float *xv = c->val + e0;
     static const bool tiled = [] { const char *e = getenv("PLSA_REF_E_TILED"); return !e || atoi(e) != 0; }();
-    if (tiled && c->nnz > 0) {
+    if (tiled && nnz > 0) {
         Scope s(c, "k_ref_e_step");
         const int kp = c->kp;
         // (PLSA_REF_FUSE_SUMS=0: no tile sums, the chain's k_ref_pair_sums reads P itself)
@@ -1485,16 +1518,17 @@ int run_ref_e_step(plsa_ctx *c, float thresh) {
         int rc_alloc = 0;
         auto go = [&](auto NZ) {
             constexpr int nz = decltype(NZ)::value;
-            const i64 tiles = (c->nnz + 64 / nz - 1) / (64 / nz);
-            if (fuse && (rc_alloc = ensure(c, c->ref_tsum.sums, sizeof(float) * (size_t)tiles * kp)) == 0) {
+            const i64 tiles = (nnz + 64 / nz - 1) / (64 / nz);
+            const i64 cap_tiles = span ? (span->cap + 64 / nz - 1) / (64 / nz) : tiles;     // (blocks: sized once, for the largest)
+            if (fuse && (rc_alloc = ensure(c, c->ref_tsum.sums, sizeof(float) * (size_t)cap_tiles * kp)) == 0) {
                 hipLaunchKernelGGL((plsa::ref::k_ref_e_step_tiled<nz, true>), dim3(grid_for(c, tiles, 2)), dim3(128),
-                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, c->rowidx.ids.as<int>(), c->col, c->nnz,
-                                   c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, c->val, c->ref_e_sw,
+                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, ri, ci, nnz,
+                                   c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, xv, c->ref_e_sw,
                                    c->ref_tsum.sums.as<float>());
                 c->ref_tsum.valid = true; c->ref_tsum.sw = c->ref_e_sw; c->ref_tsum.tj = 64 / nz;
             } else if (!rc_alloc) {
                 hipLaunchKernelGGL((plsa::ref::k_ref_e_step_tiled<nz, false>), dim3(grid_for(c, tiles, 2)), dim3(128),
-                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, c->rowidx.ids.as<int>(), c->col, c->nnz,
+                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, ri, ci, nnz,
                                    c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, nullptr, nullptr, nullptr);
             }
         };
@@ -1507,8 +1541,8 @@ int run_ref_e_step(plsa_ctx *c, float thresh) {
         if (rc_alloc) return rc_alloc;
     } else {
         Scope s(c, "k_ref_e_step");
-        hipLaunchKernelGGL(plsa::ref::k_ref_e_step, dim3(grid_for(c, c->nnz, 256)), dim3(256), 0, c->stream,
-                           c->rowidx.ids.as<int>(), c->col, c->nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
+        hipLaunchKernelGGL(plsa::ref::k_ref_e_step, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
+                           ri, ci, nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
                            p_base(c), c->kp, thresh);
     }
     CHK(launch_check(c, "k_ref_e_step"));
@@ -1542,24 +1576,33 @@ int ensure_ref_heavy(plsa_ctx *c) {
 // One chain of float32 additions over the non-zeros in order, per "topic" z < kp, WITHOUT the chain (plsa_ref_kernels.hpp: chunk
 // sums -> prefix -> (parity -> increment) pairs -> one checking walk per 64 topics), on c->ls.  kind / P / kp: PAIR_PLAIN or
 // PAIR_WEIGHTED over P(z|w,d) (norm_pwz, plsa.py:193), PAIR_NEG_TERMS over the likelihood terms with kp = 1 (plsa.py:322).
-int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const float *d_sw, float *out, unsigned long long *stats) {
-    const int *ri = c->rowidx.ids.as<int>();
+// span: the entries of one block of documents, P the block's rows; a block after the first starts its chains from `out`.
+int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const float *d_sw, float *out, unsigned long long *stats,
+                       const RefSpan *span = nullptr) {
+    const i64 e0 = span ? span->e0 : 0, nnz = span ? span->nnz : c->nnz, cap = span ? span->cap : c->nnz;
+    const bool carry = span && !span->first;
+    const int *ri = c->rowidx.ids.as<int>() + e0;
+    const float *xv = c->val + e0;
     const bool ll = kind == plsa::ref::PAIR_NEG_TERMS;              // (timing names: the likelihood's launches apart from norm_pwz's)
     // two levels (default): chunks of 256 addends, walked in groups of PAIR_R; PLSA_REF_LEVELS=1: chunks only, longer on large corpora
     bool two = true;
     if (const char *e = getenv("PLSA_REF_LEVELS")) two = atoi(e) != 1;
     int L = !two && c->nnz >= plsa::ref::PAIR_L_LARGE_FROM ? plsa::ref::PAIR_L_LARGE : plsa::ref::PAIR_L_SMALL;
     if (const char *e = getenv("PLSA_REF_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096 && v % 64 == 0) L = v; }
-    const i64 n_chunks = (c->nnz + L - 1) / L;
+    const i64 n_chunks = (nnz + L - 1) / L;
     const i64 n_groups = (n_chunks + plsa::ref::PAIR_R - 1) / plsa::ref::PAIR_R;
-    if (two) {
-        CHK(ensure(c, c->ref_pairs2, sizeof(uint4) * (size_t)n_groups * kp));
-        CHK(ensure(c, c->ref_exps2, sizeof(unsigned) * (size_t)n_groups * kp));
-    }
     const i64 n_super = (n_chunks + plsa::ref::PAIR_SC - 1) / plsa::ref::PAIR_SC, n_pad = n_super * plsa::ref::PAIR_SC;
-    CHK(ensure(c, c->ref_csum, sizeof(double) * (size_t)n_pad * kp));
-    CHK(ensure(c, c->ref_pairs, sizeof(uint4) * (size_t)n_chunks * kp));
-    CHK(ensure(c, c->ref_exps, sizeof(unsigned) * (size_t)n_chunks * kp));
+    {   // scratch for the largest span this is called with (blocks: sized once, no reallocation under the chain of the block before)
+        const i64 cap_chunks = (cap + L - 1) / L, cap_groups = (cap_chunks + plsa::ref::PAIR_R - 1) / plsa::ref::PAIR_R;
+        const i64 cap_pad = (cap_chunks + plsa::ref::PAIR_SC - 1) / plsa::ref::PAIR_SC * plsa::ref::PAIR_SC;
+        if (two) {
+            CHK(ensure(c, c->ref_pairs2, sizeof(uint4) * (size_t)cap_groups * kp));
+            CHK(ensure(c, c->ref_exps2, sizeof(unsigned) * (size_t)cap_groups * kp));
+        }
+        CHK(ensure(c, c->ref_csum, sizeof(double) * (size_t)cap_pad * kp));
+        CHK(ensure(c, c->ref_pairs, sizeof(uint4) * (size_t)cap_chunks * kp));
+        CHK(ensure(c, c->ref_exps, sizeof(unsigned) * (size_t)cap_chunks * kp));
+    }
     const int grid = grid_for(c, n_super, 4);
     double *csum = c->ref_csum.as<double>();
     uint4 *prs = c->ref_pairs.as<uint4>();
@@ -1579,21 +1622,22 @@ int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const floa
             if (!ll && c->ref_tsum.valid && c->ref_tsum.sw == d_sw && P == p_base(c) && c->p_state.valid && L % c->ref_tsum.tj == 0) {
                 // the E-step that wrote this P left the sums of its tiles: no second pass over P
                 Scope s(c, "k_ref_pair_sums");
-                const i64 n_tiles = (c->nnz + c->ref_tsum.tj - 1) / c->ref_tsum.tj;
+                const i64 n_tiles = (nnz + c->ref_tsum.tj - 1) / c->ref_tsum.tj;
                 hipLaunchKernelGGL(plsa::ref::k_ref_pair_sums_from_tiles, dim3(grid_for(c, n_chunks * kp, 256)), dim3(256), 0, c->ls,
                                    c->ref_tsum.sums.as<float>(), kp, L / c->ref_tsum.tj, n_tiles, n_chunks, n_pad, csum);
             } else {
                 Scope s(c, ll ? "k_ref_ll_pair_sums" : "k_ref_pair_sums");
-                hipLaunchKernelGGL((plsa::ref::k_ref_pair_sums<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, c->val, c->nnz, P,
+                hipLaunchKernelGGL((plsa::ref::k_ref_pair_sums<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, xv, nnz, P,
                                    d_sw, kp, L, n_chunks, n_pad, csum);
             }
             {
                 Scope s(c, ll ? "k_ref_ll_pair_prefix" : "k_ref_pair_prefix");
-                hipLaunchKernelGGL(plsa::ref::k_ref_pair_prefix, dim3(kp), dim3(256), 0, c->ls, csum, n_chunks, n_pad);
+                if (carry) hipLaunchKernelGGL(plsa::ref::k_ref_pair_prefix<true>, dim3(kp), dim3(256), 0, c->ls, csum, n_chunks, n_pad, out);
+                else hipLaunchKernelGGL(plsa::ref::k_ref_pair_prefix<false>, dim3(kp), dim3(256), 0, c->ls, csum, n_chunks, n_pad, nullptr);
             }
             {
                 Scope s(c, ll ? "k_ref_ll_pair_build" : "k_ref_pair_build");
-                hipLaunchKernelGGL((plsa::ref::k_ref_pair_build<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, c->val, c->nnz, P,
+                hipLaunchKernelGGL((plsa::ref::k_ref_pair_build<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, xv, nnz, P,
                                    d_sw, kp, L, n_chunks, n_pad, csum, prs, exps);
             }
             if (two) {
@@ -1603,13 +1647,20 @@ int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const floa
                                        kp, n_chunks, n_groups, c->ref_pairs2.as<uint4>(), c->ref_exps2.as<unsigned>());
                 }
                 Scope s(c, ll ? "k_ref_ll_pair_walk" : "k_ref_pair_walk");
-                hipLaunchKernelGGL((plsa::ref::k_ref_pair_walk<kd, true>), dim3((kp + 63) / 64), dim3(plsa::ref::WALK_THREADS), 0, c->ls, ri,
-                                   c->val, c->nnz, P, d_sw, kp, L, n_groups, c->ref_pairs2.as<uint4>(), c->ref_exps2.as<unsigned>(), out,
-                                   stats, n_chunks, prs, exps);
+                auto walk = [&](auto CARRY) {
+                    hipLaunchKernelGGL((plsa::ref::k_ref_pair_walk<kd, true, decltype(CARRY)::value>), dim3((kp + 63) / 64),
+                                       dim3(plsa::ref::WALK_THREADS), 0, c->ls, ri, xv, nnz, P, d_sw, kp, L, n_groups,
+                                       c->ref_pairs2.as<uint4>(), c->ref_exps2.as<unsigned>(), out, stats, n_chunks, prs, exps);
+                };
+                if (carry) walk(std::true_type{}); else walk(std::false_type{});
             } else {
                 Scope s(c, ll ? "k_ref_ll_pair_walk" : "k_ref_pair_walk");
-                hipLaunchKernelGGL((plsa::ref::k_ref_pair_walk<kd, false>), dim3((kp + 63) / 64), dim3(plsa::ref::WALK_THREADS), 0, c->ls, ri,
-                                   c->val, c->nnz, P, d_sw, kp, L, n_chunks, prs, exps, out, stats, n_chunks, prs, exps);
+                auto walk = [&](auto CARRY) {
+                    hipLaunchKernelGGL((plsa::ref::k_ref_pair_walk<kd, false, decltype(CARRY)::value>), dim3((kp + 63) / 64),
+                                       dim3(plsa::ref::WALK_THREADS), 0, c->ls, ri, xv, nnz, P, d_sw, kp, L, n_chunks, prs, exps, out,
+                                       stats, n_chunks, prs, exps);
+                };
+                if (carry) walk(std::true_type{}); else walk(std::false_type{});
             }
         };
         using std::integral_constant;
@@ -1627,9 +1678,14 @@ bool ref_pairs_now(const plsa_ctx *c) {
     return c->ref_chain_mode == 1 || (c->ref_chain_mode == 0 && !c->ref_pairs_off && c->nnz >= 4096);
 }
 
-int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw) {
+// span: the chain over one block's entries, started (after the first block) from what norm_pwz holds; the walk's counts add up
+// over the blocks and are read back after the last.
+int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw, const RefSpan *span) {
     const int kp = c->kp;
-    const int *ri = c->rowidx.ids.as<int>();
+    const i64 e0 = span ? span->e0 : 0, nnz = span ? span->nnz : c->nnz;
+    const bool carry = span && !span->first, last = !span || span->last;
+    const int *ri = c->rowidx.ids.as<int>() + e0;
+    const float *xv = c->val + e0;
     float *out = c->norm_pwz.as<float>();
     if (c->nnz <= 0) { HIPCHK(c, hipMemsetAsync(out, 0, sizeof(float) * (size_t)kp, c->ls)); return 0; }
     // the last walk's count of slow chunks, if it has arrived (never waited for)
@@ -1651,12 +1707,13 @@ int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw) {
     if (!pairs) {
         Scope s(c, "k_ref_norm_chain");
         by_nz([&](auto NZ) {
-            if (d_sw)
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<decltype(NZ)::value, true>), dim3(1), dim3(plsa::ref::CHAIN_THREADS), 0,
-                                   c->ls, ri, c->val, c->nnz, p_base(c), d_sw, kp, out);
-            else
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<decltype(NZ)::value, false>), dim3(1), dim3(plsa::ref::CHAIN_THREADS), 0,
-                                   c->ls, ri, c->val, c->nnz, p_base(c), d_sw, kp, out);
+            auto go = [&](auto SW, auto CARRY) {
+                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<decltype(NZ)::value, decltype(SW)::value, false, decltype(CARRY)::value>),
+                                   dim3(1), dim3(plsa::ref::CHAIN_THREADS), 0, c->ls, ri, xv, nnz, p_base(c), d_sw, kp, out,
+                                   nullptr, nullptr, nullptr, (i64)0, (i64)0, 0);
+            };
+            if (d_sw) { if (carry) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+            else { if (carry) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
         });
         return launch_check(c, "k_ref_norm_chain");
     }
@@ -1666,15 +1723,96 @@ int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw) {
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_ref_stats.h, hipEventDisableTiming));
     }
     unsigned long long *stats = c->ref_stats.as<unsigned long long>();
-    HIPCHK(c, hipMemsetAsync(stats, 0, 16, c->ls));
-    CHK(run_ref_pair_chain(c, d_sw ? plsa::ref::PAIR_WEIGHTED : plsa::ref::PAIR_PLAIN, p_base(c), kp, d_sw, out, stats));
+    if (!carry) HIPCHK(c, hipMemsetAsync(stats, 0, 16, c->ls));
+    CHK(run_ref_pair_chain(c, d_sw ? plsa::ref::PAIR_WEIGHTED : plsa::ref::PAIR_PLAIN, p_base(c), kp, d_sw, out, stats, span));
     CHK(launch_check(c, "k_ref_pair_walk"));
-    if (!c->ref_stats_pending) {       // (one read-back in flight at a time; a walk whose count is skipped is simply not counted)
+    if (last && !c->ref_stats_pending) {       // (one read-back in flight at a time; a walk whose count is skipped is simply not counted)
         HIPCHK(c, hipMemcpyAsync(c->h_ref_stats.get(), stats, 16, hipMemcpyDeviceToHost, c->ls));
         HIPCHK(c, hipEventRecord(c->ev_ref_stats, c->ls));
         c->ref_stats_pending = true;
     }
     return 0;
+}
+
+// The document pass, the column pass and the long columns of the reference M-step on c->stream, from the P(z|w,d) of all
+// non-zeros or (span) of one block of documents: that block's documents, and every column's entries inside the block with the
+// accumulators carried in Vacc from block to block.
+// (order: the length-sorted document order of the whole corpus; a block walks its documents in their own order)
+int run_ref_passes(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz, int heavy_min, const int *order,
+                   const RefSpan *span = nullptr) {
+    const int d0 = span ? span->d0 : 0, nd = span ? span->d1 - span->d0 : (int)c->n, first = !span || span->first;
+    const i64 e0 = span ? span->e0 : 0, e1 = span ? span->e0 + span->nnz : 0;
+    // the tiled document pass pays from ~300 k documents on (config 3 whole: 22 -> 10 ms); below, the wave tile that holds the few
+    // longest documents is the pass, and the group kernel walks a long document faster (PLSA_REF_ROW_TILED=1 / 0 pins either)
+    const char *row_tiled_env = getenv("PLSA_REF_ROW_TILED");
+    const bool row_tiled = row_tiled_env ? atoi(row_tiled_env) != 0 : c->n >= 300000;
+    auto blocked = [&](auto &&go) { if (span) go(std::true_type{}); else go(std::false_type{}); };
+    CHK(dispatch_ref_group(c, [&](auto G, auto NZ) {
+        constexpr int g = decltype(G)::value, nz = decltype(NZ)::value;
+        blocked([&](auto BLK) {
+            constexpr bool blk = decltype(BLK)::value;
+            if (row_tiled) {
+                Scope s(c, "k_ref_row_pass");
+                constexpr int tj = 64 / nz;
+                hipLaunchKernelGGL((plsa::ref::k_ref_row_pass_tiled<nz, blk>), dim3(grid_for(c, (nd + tj - 1) / tj, 2)), dim3(128),
+                                   sizeof(float) * 2 * tj * (size_t)(c->kp + 1), c->stream, c->indptr, c->val, nd, order,
+                                   p_base(c), c->U[out_u(c)].as<float>(), d_norm_pdz, c->kp, d0, e0);
+            } else {
+                Scope s(c, "k_ref_row_pass");
+                hipLaunchKernelGGL((plsa::ref::k_ref_row_pass<g, nz, blk>), dim3(grid_for(c, nd, 256 / g)), dim3(256),
+                                   sizeof(float) * (size_t)(256 / g) * c->kp, c->stream, c->indptr, c->val, nd, order,
+                                   p_base(c), c->U[out_u(c)].as<float>(), d_norm_pdz, c->kp, d0, e0);
+            }
+            if (update_v) {
+                Scope s(c, "k_ref_col_pass");
+                hipLaunchKernelGGL((plsa::ref::k_ref_col_pass<g, nz, blk>), dim3(grid_for(c, c->m, 256 / g)), dim3(256), 0, c->stream,
+                                   c->csc.colptr.as<int>(), c->csc.row.as<int>(), c->csc.val.as<float>(), c->csc.pos.as<int>(),
+                                   (int)c->m, p_base(c), d_sw, c->Vacc.as<float>(), c->kp, heavy_min, e0, e1, first);
+            }
+        });
+    }));
+    if (update_v && c->ref_heavy.n > 0) {
+        // the long columns: one workgroup each, the norm_pwz chain's kernel over the column's entries (6.4 ns per entry where a
+        // group's own walk costs ~160: the Zipf head was the pass -- 24.6 ms at the config-3 150 k sample, 157 ms at the whole)
+        Scope s(c, "k_ref_col_heavy");
+        const int kp = c->kp;
+        auto go = [&](auto NZ) {
+            constexpr int nz = decltype(NZ)::value;
+            auto launch = [&](auto SW, auto BLK) {
+                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, decltype(SW)::value, true, decltype(BLK)::value>),
+                                   dim3(c->ref_heavy.n), dim3(plsa::ref::CHAIN_THREADS), 0, c->stream, c->csc.row.as<int>(),
+                                   c->csc.val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(), c->csc.pos.as<int>(),
+                                   c->ref_heavy.cols.as<int>() + 1, c->csc.colptr.as<int>(), e0, e1, first);
+            };
+            blocked([&](auto BLK) { if (d_sw) launch(std::true_type{}, BLK); else launch(std::false_type{}, BLK); });
+        };
+        using std::integral_constant;
+        if (kp <= 64) go(integral_constant<int, 1>{});
+        else if (kp <= 128) go(integral_constant<int, 2>{});
+        else if (kp <= 256) go(integral_constant<int, 4>{});
+        else if (kp <= 512) go(integral_constant<int, 8>{});
+        else go(integral_constant<int, 16>{});
+    }
+    return launch_check(c, "k_ref_row_pass / k_ref_col_pass");
+}
+
+// what the vocabulary half needs before its first launch; *heavy_min: the length from which a column goes to a workgroup of its own
+int prepare_ref_v(plsa_ctx *c, int *heavy_min) {
+    CHK(ensure_csc(c));
+    CHK(ensure_rowidx(c));
+    CHK(ensure_ref_heavy(c));
+    if (c->ref_heavy.n > 0) *heavy_min = c->ref_heavy.min;
+    return ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp);
+}
+
+// after the passes and the chain (ev_join): P(w|z) = Vacc / norm_pwz where positive (plsa.py:196-199)
+int run_ref_v_normalise(plsa_ctx *c) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    Scope s(c, "k_v_normalise");
+    const i64 total4 = c->m * c->kp / 4;
+    hipLaunchKernelGGL(plsa::k_v_normalise, dim3(grid_for(c, total4, 256)), dim3(256), c->kp * sizeof(float), c->stream,
+                       c->Vacc.as<float>(), c->Vt[out_v(c)].as<float>(), (int)c->m, c->kp, c->norm_pwz.as<float>());
+    return launch_check(c, "k_v_normalise");
 }
 
 // plsa.py:172-204 / 277-310 / 795-816 from the materialised P: U[out], (update_v) Vt[out]; swaps the buffers in.
@@ -1683,14 +1821,10 @@ int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw) {
 int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz) {
     if (c->sharded) return fail(c, "the reference arithmetic has no doc-sharded form (norm_pwz is ONE chain over all non-zeros)");
     const int *order = nullptr;
-    CHK(ensure_roworder(c, &order));
+    CHK(ensure_roworder(c, &order));               // (here: the sort is enqueued before the fork to the second stream)
     int heavy_min = INT32_MAX;
     if (update_v) {
-        CHK(ensure_csc(c));
-        CHK(ensure_rowidx(c));
-        CHK(ensure_ref_heavy(c));
-        if (c->ref_heavy.n > 0) heavy_min = c->ref_heavy.min;
-        CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
+        CHK(prepare_ref_v(c, &heavy_min));
         HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
         {
@@ -1700,65 +1834,122 @@ int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_
         CHK(launch_check(c, "k_ref_norm_chain"));
         HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
     }
-    // the tiled document pass pays from ~300 k documents on (config 3 whole: 22 -> 10 ms); below, the wave tile that holds the few
-    // longest documents is the pass, and the group kernel walks a long document faster (PLSA_REF_ROW_TILED=1 / 0 pins either)
-    const char *row_tiled_env = getenv("PLSA_REF_ROW_TILED");
-    const bool row_tiled = row_tiled_env ? atoi(row_tiled_env) != 0 : c->n >= 300000;
-    CHK(dispatch_ref_group(c, [&](auto G, auto NZ) {
-        constexpr int g = decltype(G)::value, nz = decltype(NZ)::value;
-        if (row_tiled) {
-            Scope s(c, "k_ref_row_pass");
-            constexpr int tj = 64 / nz;
-            hipLaunchKernelGGL((plsa::ref::k_ref_row_pass_tiled<nz>), dim3(grid_for(c, (c->n + tj - 1) / tj, 2)), dim3(128),
-                               sizeof(float) * 2 * tj * (size_t)(c->kp + 1), c->stream, c->indptr, c->val, (int)c->n, order,
-                               p_base(c), c->U[out_u(c)].as<float>(), d_norm_pdz, c->kp);
-        } else {
-            Scope s(c, "k_ref_row_pass");
-            hipLaunchKernelGGL((plsa::ref::k_ref_row_pass<g, nz>), dim3(grid_for(c, c->n, 256 / g)), dim3(256),
-                               sizeof(float) * (size_t)(256 / g) * c->kp, c->stream, c->indptr, c->val, (int)c->n, order,
-                               p_base(c), c->U[out_u(c)].as<float>(), d_norm_pdz, c->kp);
-        }
-        if (update_v) {
-            Scope s(c, "k_ref_col_pass");
-            hipLaunchKernelGGL((plsa::ref::k_ref_col_pass<g, nz>), dim3(grid_for(c, c->m, 256 / g)), dim3(256), 0, c->stream,
-                               c->csc.colptr.as<int>(), c->csc.row.as<int>(), c->csc.val.as<float>(), c->csc.pos.as<int>(),
-                               (int)c->m, p_base(c), d_sw, c->Vacc.as<float>(), c->kp, heavy_min);
-        }
-    }));
-    if (update_v && c->ref_heavy.n > 0) {
-        // the long columns: one workgroup each, the norm_pwz chain's kernel over the column's entries (6.4 ns per entry where a
-        // group's own walk costs ~160: the Zipf head was the pass -- 24.6 ms at the config-3 150 k sample, 157 ms at the whole)
-        Scope s(c, "k_ref_col_heavy");
-        const int kp = c->kp;
-        auto go = [&](auto NZ) {
-            constexpr int nz = decltype(NZ)::value;
-            if (d_sw)
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, true, true>), dim3(c->ref_heavy.n), dim3(plsa::ref::CHAIN_THREADS), 0,
-                                   c->stream, c->csc.row.as<int>(), c->csc.val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(),
-                                   c->csc.pos.as<int>(), c->ref_heavy.cols.as<int>() + 1, c->csc.colptr.as<int>());
-            else
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, false, true>), dim3(c->ref_heavy.n), dim3(plsa::ref::CHAIN_THREADS), 0,
-                                   c->stream, c->csc.row.as<int>(), c->csc.val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(),
-                                   c->csc.pos.as<int>(), c->ref_heavy.cols.as<int>() + 1, c->csc.colptr.as<int>());
-        };
-        using std::integral_constant;
-        if (kp <= 64) go(integral_constant<int, 1>{});
-        else if (kp <= 128) go(integral_constant<int, 2>{});
-        else if (kp <= 256) go(integral_constant<int, 4>{});
-        else if (kp <= 512) go(integral_constant<int, 8>{});
-        else go(integral_constant<int, 16>{});
-    }
-    CHK(launch_check(c, "k_ref_row_pass / k_ref_col_pass"));
-    if (update_v) {
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        Scope s(c, "k_v_normalise");
-        const i64 total4 = c->m * c->kp / 4;
-        hipLaunchKernelGGL(plsa::k_v_normalise, dim3(grid_for(c, total4, 256)), dim3(256), c->kp * sizeof(float), c->stream,
-                           c->Vacc.as<float>(), c->Vt[out_v(c)].as<float>(), (int)c->m, c->kp, c->norm_pwz.as<float>());
-        CHK(launch_check(c, "k_v_normalise"));
-    }
+    CHK(run_ref_passes(c, d_sw, update_v, d_norm_pdz, heavy_min, order));
+    if (update_v) CHK(run_ref_v_normalise(c));
     c->cu ^= 1;
     if (update_v) c->cv ^= 1;
+    return 0;
+}
+
+// The block plan of plsa_set_p_budget for the active matrix: whole documents, in order, as many per block as
+// (block_nnz + 64) * kp * 4 <= budget allows.  (The 64 rows are the slack the tiled E-step stores its last tile into.)
+int ensure_ref_blocks(plsa_ctx *c) {
+    plsa_ctx::RefBlocks &pl = c->ref_blocks;
+    if (pl.valid && pl.budget == c->p_budget && pl.kp == c->kp) return 0;
+    pl.valid = false;                              // (a rebuild that fails leaves no plan behind)
+    const int64_t row_bytes = (int64_t)sizeof(float) * c->kp;
+    const i64 max_rows = c->p_budget / row_bytes - 64;
+    if (max_rows < 1)
+        return fail(c, "plsa_set_p_budget: a budget of %lld bytes holds no row of P(z|w,d): the least usable budget at k = %d is "
+                       "%lld bytes ((1 + 64) * %d * 4)", (long long)c->p_budget, c->k, (long long)(65 * row_bytes), c->kp);
+    pl.doc.assign(1, 0); pl.ent.assign(1, 0);
+    pl.budget = c->p_budget; pl.kp = c->kp; pl.largest = 0;
+    if (c->nnz <= max_rows) {
+        pl.doc.push_back(c->n); pl.ent.push_back(c->nnz);
+        pl.largest = c->nnz;
+    } else {
+        std::vector<int> ip((size_t)c->n + 1);
+        HIPCHK(c, hipMemcpyAsync(ip.data(), c->indptr, sizeof(int) * ip.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        i64 b0 = 0;                                // first entry of the block being filled
+        for (i64 d = 0; d < c->n; ++d) {
+            const i64 len = (i64)ip[d + 1] - ip[d];
+            if (len > max_rows)
+                return fail(c, "plsa_set_p_budget: document %lld has %lld non-zeros, its P(z|w,d) rows alone need %lld bytes "
+                               "((non-zeros + 64) * %d * 4) and the budget is %lld bytes", (long long)d, (long long)len,
+                            (long long)((len + 64) * row_bytes), c->kp, (long long)c->p_budget);
+            if ((i64)ip[d + 1] - b0 > max_rows) {  // document d opens the next block
+                pl.doc.push_back(d); pl.ent.push_back(ip[d]);
+                pl.largest = std::max(pl.largest, (i64)ip[d] - b0);
+                b0 = ip[d];
+            }
+        }
+        pl.doc.push_back(c->n); pl.ent.push_back(c->nnz);
+        pl.largest = std::max(pl.largest, c->nnz - b0);
+    }
+    pl.valid = true;
+    return 0;
+}
+
+// One EM iteration of the reference arithmetic with P(z|w,d) of ONE BLOCK of documents at a time (plsa_set_p_budget): per block
+// the E-step of its entries, its documents' half of the M-step (complete inside the block), and its part of every column's chain
+// and of the norm_pwz chain, each started from what the block before left (Vacc, norm_pwz) -- the additions of run_ref_m_step in
+// the same order.  Streams: the norm_pwz chain of block b runs on the second stream beside the passes of block b, as in the
+// unblocked step; the E-step of block b + 1 overwrites the buffer, so it waits for that chain (ev_join) and, in stream order, for
+// the passes; chain b + 1 follows chain b in the second stream's own order.
+int run_ref_em_blocked(plsa_ctx *c, float thresh, const float *d_sw, bool update_v) {
+    if (c->sharded) return fail(c, "the reference arithmetic has no doc-sharded form (norm_pwz is ONE chain over all non-zeros)");
+    const plsa_ctx::RefBlocks &pl = c->ref_blocks;
+    c->ref_tsum.invalidate(); c->p_state.invalidate();
+    CHK(ensure_p(c, pl.largest));
+    CHK(ensure_rowidx(c));
+    int heavy_min = INT32_MAX;
+    if (update_v) CHK(prepare_ref_v(c, &heavy_min));
+    // (whatever way the loop is left: P holds one block, not the responsibilities of the matrix)
+    struct Forget { plsa_ctx *c; ~Forget() { c->ref_tsum.invalidate(); c->p_state.invalidate(); } } forget{c};
+    const int nb = pl.blocks();
+    for (int b = 0; b < nb; ++b) {
+        const RefSpan span{pl.ent[b], pl.ent[b + 1] - pl.ent[b], (int)pl.doc[b], (int)pl.doc[b + 1], pl.largest, b == 0, b == nb - 1};
+        if (update_v && b > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));     // the chain of block b - 1 has read P
+        c->ref_tsum.invalidate();
+        CHK(run_ref_e_step(c, thresh, &span));
+        if (update_v) {
+            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+            {
+                LaunchOn on2(c, c->stream2);
+                CHK(run_ref_norm_pwz(c, d_sw, &span));
+            }
+            CHK(launch_check(c, "k_ref_norm_chain"));
+            HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+        }
+        CHK(run_ref_passes(c, d_sw, update_v, nullptr, heavy_min, nullptr, &span));
+    }
+    if (update_v) CHK(run_ref_v_normalise(c));
+    c->cu ^= 1;
+    if (update_v) c->cv ^= 1;
+    return 0;
+}
+
+// One materialised EM iteration of a driver (plsa_fit, plsa_refit): E-step into P(z|w,d), M-step from it -- in the reference
+// arithmetic under a budget (plsa_set_p_budget) block by block when the plan has more than one block.
+int run_driver_iteration(plsa_ctx *c, float thresh, const float *d_sw, bool update_v) {
+    bool blocked = false;
+    if (c->ref_sums && c->p_budget > 0) {
+        if (c->P.borrowed || c->p_lent)
+            return fail(c, "plsa_set_p_budget: a budget and a P(z|w,d) buffer that is %s do not mix -- end the loan or set the budget to 0",
+                        c->P.borrowed ? "borrowed (plsa_p_borrow)" : "lent out (plsa_p_reserve)");
+        CHK(ensure_ref_blocks(c));
+        blocked = c->ref_blocks.blocks() > 1;
+        if (c->P.cap > (size_t)c->p_budget) {      // left by a call without the budget: it goes before anything is allocated
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream2));
+            c->P.release();
+            c->p_state.invalidate();
+        }
+    }
+    if (blocked) CHK(run_ref_em_blocked(c, thresh, d_sw, update_v));
+    else {
+        CHK(run_e_step(c, thresh));
+        CHK(run_m_step_from_p(c, d_sw, update_v, nullptr));
+    }
+    if (c->ref_sums) {
+        plsa_ctx::PBlockInfo &pi = c->p_block_info;
+        pi.budget = c->p_budget;
+        pi.blocks = blocked ? c->ref_blocks.blocks() : 1;
+        pi.largest = blocked ? c->ref_blocks.largest : c->nnz;
+        pi.p_bytes = (int64_t)c->P.cap;
+    }
     return 0;
 }
 
@@ -2368,8 +2559,7 @@ int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_te
         struct ESw { plsa_ctx *c; ~ESw() { c->ref_e_sw = nullptr; } } e_sw_guard{c};
         c->ref_e_sw = d_sw_m;               // (reference arithmetic: the E-step leaves its tile sums with the weights the M-step will use)
         for (int i = 0; i < n_iter; ++i) {
-            CHK(run_e_step(c, thresh));                              // plsa.py:597
-            CHK(run_m_step_from_p(c, d_sw_m, true, nullptr));       // plsa.py:606-628
+            CHK(run_driver_iteration(c, thresh, d_sw_m, true));      // plsa.py:597, 606-628
             iters++;
             if (i % n_iter_per_test == 0) {                          // plsa.py:630
                 if (i == n_iter - 1 && !trace) break;                // outcome cannot matter any more
@@ -2633,8 +2823,7 @@ int plsa_refit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_
         struct NoSums { plsa_ctx *c; ~NoSums() { c->ref_e_no_sums = false; } } no_sums_guard{c};
         c->ref_e_no_sums = true;            // (reference arithmetic: no norm_pwz chain follows these E-steps, their tile sums would be wasted)
         for (int i = 0; i < n_iter; ++i) {
-            CHK(run_e_step(c, thresh));
-            CHK(run_m_step_from_p(c, nullptr, false, nullptr));
+            CHK(run_driver_iteration(c, thresh, nullptr, false));
             iters++;
             if (i % n_iter_per_test == 0) {
                 if (i == n_iter - 1 && !trace) break;
@@ -2969,6 +3158,22 @@ int plsa_reference_chain_info(plsa_ctx *c, int64_t *slow_chunks, int64_t *chunks
     return 0;
 }
 
+// include/plsa_hip_blocked.h
+int plsa_set_p_budget(plsa_ctx *c, int64_t bytes) {
+    if (bytes < 0) return fail(c, "plsa_set_p_budget: %lld bytes (0: no budget)", (long long)bytes);
+    c->p_budget = bytes;
+    return 0;
+}
+
+int plsa_p_block_info(plsa_ctx *c, int64_t *budget, int32_t *blocks, int64_t *largest_block_nnz, int64_t *p_allocated_bytes) {
+    const plsa_ctx::PBlockInfo &pi = c->p_block_info;
+    if (budget) *budget = pi.budget;
+    if (blocks) *blocks = pi.blocks;
+    if (largest_block_nnz) *largest_block_nnz = pi.largest;
+    if (p_allocated_bytes) *p_allocated_bytes = pi.p_bytes;
+    return 0;
+}
+
 int plsa_placement_info(plsa_ctx *c, int32_t *candidates, double *best_gbps, double *worst_gbps) {
     if (candidates) *candidates = c->placement_tried;
     if (best_gbps) *best_gbps = c->placement_gbps[0];
@@ -3020,7 +3225,7 @@ int plsa_release_scratch(plsa_ctx *c) {
     c->p_shift = 0;
     // derived structures kept only for the reference arithmetic / the fused passes: rebuilt on demand (the packed entry
     // streams by the next fused pass, from the CSC arrays, which stay)
-    c->ref_heavy.drop(); c->ref_tsum.drop(); c->pk_csr.drop(); c->pk_csc.drop();
+    c->ref_heavy.drop(); c->ref_tsum.drop(); c->ref_blocks.drop(); c->pk_csr.drop(); c->pk_csc.drop();
     for (DevBuf *b : {&c->ref_terms, &c->ref_csum, &c->ref_pairs, &c->ref_exps, &c->ref_ll_neg, &c->ref_pairs2, &c->ref_exps2,
                       &c->partial, &c->tmp0, &c->tmp1, &c->tmp2, &c->cubtmp, &c->pk_count,
                       &c->mt_words, &c->mt_state, &c->mt_fin, &c->mt_poly, &c->mt_seq,

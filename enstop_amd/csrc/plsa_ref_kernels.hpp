@@ -48,6 +48,22 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
+// DOCUMENT BLOCKS (plsa_set_p_budget): the corpus cut at document boundaries, block b = documents [d0, d1) = entries [e0, e1) of the
+// COO order, and P holding the rows of THAT block only (row e - e0).  Every chain of the M-step runs over the non-zeros in COO
+// order, so it is either complete inside one block (a document's sums) or handed from block to block: the value a block leaves
+// (Vacc[w], norm_pwz[z]) is where the next block's accumulator starts -- the same additions in the same order, the same bits.
+// The kernels below take the block as template-gated arguments (RANGE / CARRY = false: the whole corpus, the arguments unused).
+//
+// a column's entries of the block: its csc_pos ascend (stable CSC), so they are one contiguous sub-range -- first index in
+// [lo, hi) whose position is >= v
+__device__ __forceinline__ int pos_lower_bound(const int *__restrict__ pos, int lo, int hi, i64 v) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if ((i64)pos[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // ------------------------------------------------------------------------------------------------
 // plsa.py:91-105.  One lane per non-zero: the topics are walked in order z = 0 .. k-1 with ONE float32
 // norm (plsa.py:33 types it float32), kept products divided by it (true division) when it is positive.
@@ -204,11 +220,13 @@ __global__ __launch_bounds__(256) void k_ref_pair_sums_from_tiles(const float *_
 // lane's own sums p_z_given_d[d, z] += s, and norm_pdz[d] += s for z = 0 .. k-1 IN THAT ORDER: the group's products go
 // through LDS and every lane adds them one by one (all lanes of a group carry the same chain).
 // ------------------------------------------------------------------------------------------------
-template <int G, int NZ>
+// RANGE: the documents d0 .. d0 + n - 1 of a block in their own order, P row j at (j - e0).
+template <int G, int NZ, bool RANGE = false>
 __global__ __launch_bounds__(256) void k_ref_row_pass(const int *__restrict__ indptr, const float *__restrict__ vals,
                                                       int n, const int *__restrict__ row_order,
                                                       const float *__restrict__ P, float *__restrict__ U_new,
-                                                      float *__restrict__ norm_pdz_out, int kp) {
+                                                      float *__restrict__ norm_pdz_out, int kp, int d0 = 0, i64 e0 = 0) {
+    const i64 pe = RANGE ? e0 : 0;            // P row of entry j: j - pe
     extern __shared__ float s_lds[];          // [256 / G][kp]
     constexpr int GPB = 256 / G;
     const int li = threadIdx.x % G, gid = threadIdx.x / G;
@@ -216,7 +234,7 @@ __global__ __launch_bounds__(256) void k_ref_row_pass(const int *__restrict__ in
     const float4 *mine4 = reinterpret_cast<const float4 *>(mine);
     const int q = kp >> 2;
     for (i64 r = (i64)blockIdx.x * GPB + gid; r < n; r += (i64)gridDim.x * GPB) {
-        const int d = row_order ? row_order[r] : (int)r;
+        const int d = RANGE ? d0 + (int)r : (row_order ? row_order[r] : (int)r);
         const int j0 = indptr[d], j1 = indptr[d + 1];
         float acc[NZ];
 #pragma unroll
@@ -229,7 +247,7 @@ __global__ __launch_bounds__(256) void k_ref_row_pass(const int *__restrict__ in
         if (j0 < j1) {
             xn = vals[j0];
 #pragma unroll
-            for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) pn[t] = P[(i64)j0 * kp + z]; }
+            for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) pn[t] = P[((i64)j0 - pe) * kp + z]; }
         }
         for (int j = j0; j < j1; ++j) {
             const float x = xn;
@@ -239,7 +257,7 @@ __global__ __launch_bounds__(256) void k_ref_row_pass(const int *__restrict__ in
             if (j + 1 < j1) {
                 xn = vals[j + 1];
 #pragma unroll
-                for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) pn[t] = P[(i64)(j + 1) * kp + z]; }
+                for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) pn[t] = P[((i64)(j + 1) - pe) * kp + z]; }
             }
 #pragma unroll
             for (int t = 0; t < NZ; ++t) {
@@ -272,12 +290,13 @@ __global__ __launch_bounds__(256) void k_ref_row_pass(const int *__restrict__ in
 // parks + 0.0; (B) lane = document -- norm_pdz[d] += s over the tile row, z ascending: the reference's chain (entry-major, z-minor),
 // ONE lane per document adding it where the group kernel above has all its lanes carry the same chain, sixteen documents' worth of
 // dependent additions per wave instruction instead of four (config 3 whole: 22 ms at 1.1 TB/s).
-template <int NZ>
+template <int NZ, bool RANGE = false>
 __global__ __launch_bounds__(128) void k_ref_row_pass_tiled(const int *__restrict__ indptr, const float *__restrict__ vals,
                                                             int n, const int *__restrict__ row_order,
                                                             const float *__restrict__ P, float *__restrict__ U_new,
-                                                            float *__restrict__ norm_pdz_out, int kp) {
+                                                            float *__restrict__ norm_pdz_out, int kp, int d0 = 0, i64 e0 = 0) {
     constexpr int TJ = 64 / NZ;
+    const i64 pe = RANGE ? e0 : 0;                               // P row of entry j: j - pe
     extern __shared__ float r_lds[];                             // [2 waves][TJ][kp + 1]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int stride = kp + 1;
@@ -288,8 +307,8 @@ __global__ __launch_bounds__(128) void k_ref_row_pass_tiled(const int *__restric
         const int cnt = (int)min((i64)TJ, (i64)n - r0);          // (uniform)
         // lane j < cnt: its document, first entry, length
         const bool has = lane < cnt;
-        const int dj = has ? (row_order ? row_order[r0 + lane] : (int)(r0 + lane)) : 0;
-        const int j0 = has ? indptr[dj] : 0;
+        const int dj = has ? (RANGE ? d0 + (int)(r0 + lane) : (row_order ? row_order[r0 + lane] : (int)(r0 + lane))) : (RANGE ? d0 : 0);
+        const int j0 = has ? indptr[dj] : (int)pe;               // (no document: the first row of P, never used)
         const int len = has ? indptr[dj + 1] - j0 : 0;
         int maxlen = len;
 #pragma unroll
@@ -308,7 +327,7 @@ __global__ __launch_bounds__(128) void k_ref_row_pass_tiled(const int *__restric
 #pragma unroll
             for (int j = 0; j < TJ; ++j) {
                 const int lj = __builtin_amdgcn_readlane(len, j);
-                const i64 at = (i64)(__builtin_amdgcn_readlane(j0, j) + (e < lj ? e : 0)) * kp;   // (a finished document: its first row
+                const i64 at = ((i64)(__builtin_amdgcn_readlane(j0, j) + (e < lj ? e : 0)) - pe) * kp;   // (a finished document: its first row
 #pragma unroll                                                                                    //  again -- cached, never used)
                 for (int q = 0; q < NZ; ++q) {
                     const int z = lane + 64 * q;
@@ -374,24 +393,39 @@ __global__ __launch_bounds__(128) void k_ref_row_pass_tiled(const int *__restric
 // Un-normalised sums -> Vacc [m, kp]; B rows of P are in flight per group.  Columns of heavy_min entries and more are left to
 // k_ref_norm_chain<.., GATHER> (one workgroup per column: ~6 ns per entry where this walk costs ~160).
 // ------------------------------------------------------------------------------------------------
-template <int G, int NZ>
+// CARRY (a block of documents, entries [e0, e1) of the COO order): the column's entries whose position lies in the block, the
+// accumulators started from what the blocks before left in Vacc[w] (first: from + 0.0); a column without an entry in the block
+// keeps its Vacc, in the first block it gets the zeros an empty column gets.
+template <int G, int NZ, bool CARRY = false>
 __global__ __launch_bounds__(256) void k_ref_col_pass(const int *__restrict__ colptr, const int *__restrict__ csc_row,
                                                       const float *__restrict__ csc_val, const int *__restrict__ csc_pos,
                                                       int m, const float *__restrict__ P, const float *__restrict__ sw,
-                                                      float *__restrict__ Vacc, int kp, int heavy_min) {
+                                                      float *__restrict__ Vacc, int kp, int heavy_min,
+                                                      i64 e0 = 0, i64 e1 = 0, int first = 1) {
+    const i64 pe = CARRY ? e0 : 0;              // P row of position q: q - pe
     constexpr int GPB = 256 / G;
     constexpr int B = NZ <= 2 ? 16 : 8;         // rows of P in flight per group
     const int li = threadIdx.x % G, gid = threadIdx.x / G;
     for (i64 w = (i64)blockIdx.x * GPB + gid; w < m; w += (i64)gridDim.x * GPB) {
-        const int j0 = colptr[w], j1 = colptr[w + 1];
+        int j0 = colptr[w], j1 = colptr[w + 1];
         if (j1 - j0 >= heavy_min) continue;     // a long column: a workgroup of its own (k_ref_norm_chain<.., GATHER>)
+        if (CARRY) {
+            j0 = pos_lower_bound(csc_pos, j0, j1, e0);
+            j1 = pos_lower_bound(csc_pos, j0, j1, e1);
+        }
         float acc[NZ];
 #pragma unroll
         for (int t = 0; t < NZ; ++t) acc[t] = 0.0f;
         if (j0 >= j1) {
+            if (!CARRY || first) {
 #pragma unroll
-            for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) Vacc[w * kp + z] = 0.0f; }
+                for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) Vacc[w * kp + z] = 0.0f; }
+            }
             continue;
+        }
+        if (CARRY && !first) {
+#pragma unroll
+            for (int t = 0; t < NZ; ++t) { const int z = li + G * t; if (z < kp) acc[t] = Vacc[w * kp + z]; }
         }
         // The Zipf-head columns are the long pole (one group walks up to n entries): the entry records (position in CSR order,
         // count, document weight) of the NEXT batch are requested while the current batch's rows of P are in flight, so a batch
@@ -417,7 +451,7 @@ __global__ __launch_bounds__(256) void k_ref_col_pass(const int *__restrict__ co
 #pragma unroll
                 for (int t = 0; t < NZ; ++t) {
                     const int z = li + G * t;
-                    p[b][t] = z < kp ? P[pos_n[b] * kp + z] : 0.0f;
+                    p[b][t] = z < kp ? P[(pos_n[b] - pe) * kp + z] : 0.0f;
                 }
             }
             load_records(min(jb + B, j1 - 1));     // (past the end: the last entry again, never added)
@@ -482,7 +516,11 @@ constexpr int CHAIN_DEPTH = 4;                         // tiles in flight in reg
 // multiplies is found through `pos` (its position in COO order), and the sums go to Vacc[w].  A load that depends on a load in a pipe
 // whose counter retires in order: the positions are requested 2 CHAIN_DEPTH tiles ahead, the rows they point to CHAIN_DEPTH tiles
 // ahead, so that waiting for a position never means waiting for the rows requested after it.
-template <int NZ, bool HAS_SW, bool GATHER = false>
+//
+// CARRY (a block of documents, entries [e0, e1) of the COO order; P holds the block's rows): the accumulators start from what the
+// blocks before left in the output (norm_pwz, Vacc[w]) unless `first`.  The chain itself is handed the block's part of the entry
+// arrays; GATHER takes the column's entries whose position lies in the block and finds their rows of P at (position - e0).
+template <int NZ, bool HAS_SW, bool GATHER = false, bool CARRY = false>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_ref_norm_chain(const int *__restrict__ rowidx,
                                                                   const float *__restrict__ vals, i64 nnz,
                                                                   const float *__restrict__ P,
@@ -490,15 +528,26 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_ref_norm_chain(const int *__r
                                                                   float *__restrict__ norm_pwz,
                                                                   const int *__restrict__ pos = nullptr,
                                                                   const int *__restrict__ heavy = nullptr,
-                                                                  const int *__restrict__ colptr = nullptr) {
+                                                                  const int *__restrict__ colptr = nullptr,
+                                                                  i64 e0 = 0, i64 e1 = 0, int first = 1) {
     constexpr int STRIDE = 64 * NZ;                            // floats between two rows of a tile in LDS
     constexpr int ROWS = CHAIN_TILE / STRIDE;                  // rows per tile (128 / NZ)
     __shared__ float4 tile[2][CHAIN_TILE / 4];
+    const i64 pe = GATHER && CARRY ? e0 : 0;                   // GATHER: P row of position q: q - pe
     if (GATHER) {                                              // (uniform: scalar registers)
-        const int w = heavy[blockIdx.x], j0 = colptr[w];
-        nnz = colptr[w + 1] - j0;
+        const int w = heavy[blockIdx.x];
+        int j0 = colptr[w], j1 = colptr[w + 1];
+        if (CARRY) {
+            j0 = pos_lower_bound(pos, j0, j1, e0);
+            j1 = pos_lower_bound(pos, j0, j1, e1);
+        }
+        nnz = j1 - j0;
         rowidx += j0; vals += j0; pos += j0;
         norm_pwz += (i64)w * kp;
+    }
+    if (CARRY && nnz <= 0) {                                   // (uniform) nothing of this chain in the block: the sums stay, or
+        if (first && threadIdx.x < kp) norm_pwz[threadIdx.x] = 0.0f;   // (first block) are the zeros an empty chain leaves
+        return;
     }
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform by construction: scalar branches below)
@@ -540,7 +589,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_ref_norm_chain(const int *__r
 #pragma unroll
         for (int s = 0; s < CHAIN_F4; ++s) {
             const bool ok = sval[s] && srow[s] < rows;
-            if (GATHER) dp[s] = *reinterpret_cast<const float4 *>(P + (i64)dq[s] * kp + scol[s]);   // (dq: a valid entry's position always)
+            if (GATHER) dp[s] = *reinterpret_cast<const float4 *>(P + ((i64)dq[s] - pe) * kp + scol[s]);   // (dq: a valid entry's position always)
             else dp[s] = *reinterpret_cast<const float4 *>(Pt + (ok ? soff[s] : 0));
             dx[s] = xt[ok ? srow[s] : 0];
             dw[s] = HAS_SW ? sw[rt[ok ? srow[s] : 0]] : 1.0f;
@@ -560,6 +609,10 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_ref_norm_chain(const int *__r
     float acc[NZ];
 #pragma unroll
     for (int t = 0; t < NZ; ++t) acc[t] = 0.0f;
+    if (CARRY && !first && wave == 0) {                          // the chain goes on where the block before stopped
+#pragma unroll
+        for (int t = 0; t < NZ; ++t) { const int z = tid + 64 * t; if (z < kp) acc[t] = norm_pwz[z]; }
+    }
     if (wave == 0) {
         // the adding wave: tile t is complete in LDS after barrier t; the producers refill that buffer after barrier t + 1 at
         // the earliest, which this wave reaches only when it is done with tile t
@@ -757,11 +810,14 @@ __global__ __launch_bounds__(256) void k_ref_pair_sums(const int *__restrict__ r
 // csum[z][:] -> its exclusive prefix sums, in place; one workgroup per topic, tiles of 2048 chunks (8 consecutive sums per lane, a
 // block-wide scan of the lanes' totals, a running carry).  Any summation order will do: the walk checks every guess.  (First
 // version: every lane scanned a slab of its own, then added up the slabs in front of it: 4 ms for the 392 k chunks of config 3.)
-__global__ __launch_bounds__(256) void k_ref_pair_prefix(double *__restrict__ csum, i64 n_chunks, i64 n_pad) {
+// CARRY (a block of documents): the chain enters the block at start[z], so that is where the prefixes begin.
+template <bool CARRY = false>
+__global__ __launch_bounds__(256) void k_ref_pair_prefix(double *__restrict__ csum, i64 n_chunks, i64 n_pad,
+                                                         const float *__restrict__ start = nullptr) {
     typedef hipcub::BlockScan<double, 256> Scan;
     __shared__ typename Scan::TempStorage tmp;
     double *a = csum + (i64)blockIdx.x * n_pad;
-    double carry = 0.0;
+    double carry = CARRY ? (double)start[blockIdx.x] : 0.0;
     for (i64 base = 0; base < n_chunks; base += 2048) {
         const i64 i0 = base + (i64)threadIdx.x * 8;
         double v[8], tot = 0.0;
@@ -944,7 +1000,9 @@ constexpr int WALK_DEPTH = 6;                          // tiles in flight in the
 constexpr int WALK_TC = 16;                            // chunks per LDS tile: 16 KB of pairs + 4 KB of exponents, two tiles
 constexpr int WALK_SLOTS = (WALK_TC * 64 + WALK_PRODUCERS - 1) / WALK_PRODUCERS;     // records per producer lane and tile (3)
 
-template <int KIND, bool TWO>
+// CARRY (a block of documents): the sum starts from the bits the block before left in norm_pwz instead of + 0.0; the checks
+// below do not care where a sum comes from, so the result stays independent of the guesses.
+template <int KIND, bool TWO, bool CARRY = false>
 __global__ __launch_bounds__(WALK_THREADS) void k_ref_pair_walk(const int *__restrict__ rowidx, const float *__restrict__ vals, i64 nnz,
                                                                  const float *__restrict__ P, const float *__restrict__ sw, int kp, int PAIR_L,
                                                                  i64 n_chunks, const uint4 *__restrict__ pairs_,
@@ -975,6 +1033,10 @@ __global__ __launch_bounds__(WALK_THREADS) void k_ref_pair_walk(const int *__res
         unsigned es = 0u, m = 0u;                                // the sum: + 0.0
         const bool mine = tid < width;
         const int z = z0 + (mine ? tid : 0);
+        if (CARRY && mine) {
+            const unsigned b = __float_as_uint(norm_pwz[z]);
+            es = b >> 23; m = es ? (b & 0x7FFFFFu) | 0x800000u : b;
+        }
         unsigned long long slow = 0;
         for (i64 t = 0; t < n_padded; ++t) {
             __syncthreads();

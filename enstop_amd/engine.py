@@ -80,6 +80,7 @@ class Engine:
         self.device = dev
         self.k = 0
         self.base_rows = 0
+        self.p_budget = 0              # set_p_budget
         # a context is not thread-safe: callers that share the process-wide engine (the reference is
         # driven from dask/joblib thread pools, enstop_.py:209-217) serialise on this lock
         self.lock = threading.RLock()
@@ -312,6 +313,21 @@ class Engine:
         """bytes of P(z|w,d) for the active matrix and the factors in force (one tile of slack included)"""
         n, m, nnz = self.shape
         return 4 * (nnz + 64) * ((self.k + 3) // 4 * 4)
+
+    def set_p_budget(self, nbytes=0):
+        """Bytes P(z|w,d) may take in fit / refit in the reference arithmetic (plsa_set_p_budget; 0 or None: no budget): the
+        documents are then walked in blocks that fit, with the same bits as the unblocked step.  No effect on the default
+        arithmetic (its fused schedule stores no P) nor on e_step / m_step / set_p, which hand the whole array in or out."""
+        self._ok(self._L.plsa_set_p_budget(self._h, int(nbytes or 0)))
+        self.p_budget = int(nbytes or 0)
+        return self
+
+    def p_block_info(self):
+        """Of the last reference-arithmetic iteration of fit / refit (plsa_p_block_info): the budget in force, the blocks it ran
+        in, the non-zeros of the largest block, the bytes allocated for P(z|w,d)."""
+        a, b, c_, d = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._ok(self._L.plsa_p_block_info(self._h, C.byref(a), C.byref(b), C.byref(c_), C.byref(d)))
+        return dict(budget=a.value, blocks=b.value, largest_block_nnz=c_.value, p_allocated_bytes=d.value)
 
     def p_reserve(self, nbytes):
         """own P(z|w,d) capacity of at least nbytes; returns its device address (for p_borrow on other contexts)"""

@@ -82,6 +82,28 @@ class _KernelArithmetic:
         self.eng.set_arithmetic(None)
 
 
+class _PBudget:
+    """`p_budget=` of ONE fit / refit on the shared engine: bytes P(z|w,d) may take in the reference arithmetic
+    (Engine.set_p_budget: the documents are walked in blocks that fit, same bits).  None reads ENSTOP_AMD_P_BUDGET_MB
+    (unset: no budget).  No effect outside the reference arithmetic.  The engine gets its previous budget back."""
+
+    def __init__(self, eng, p_budget):
+        self.eng = eng
+        if p_budget is None:
+            mb = os.environ.get("ENSTOP_AMD_P_BUDGET_MB") or None
+            p_budget = None if mb is None else int(float(mb) * (1 << 20))
+        self.p_budget = p_budget
+
+    def __enter__(self):
+        self.before = getattr(self.eng, "p_budget", 0)
+        if self.p_budget is not None:
+            self.eng.set_p_budget(self.p_budget)
+
+    def __exit__(self, *exc):
+        if self.p_budget is not None:
+            self.eng.set_p_budget(self.before)
+
+
 def _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device=None, arithmetic=None):
     k, m = p_w_given_z.shape
     n = p_z_given_d.shape[0]
@@ -283,19 +305,23 @@ def _fit_on_engine(eng, k, sample_weight, init, n_iter, n_iter_per_test, toleran
 
 @_locked
 def plsa_fit(X, k, sample_weight, init="random", n_iter=100, n_iter_per_test=10, tolerance=0.001,
-             e_step_thresh=1e-32, random_state=None, device=None, flags=None, return_info=False, arithmetic=None):
+             e_step_thresh=1e-32, random_state=None, device=None, flags=None, return_info=False, arithmetic=None,
+             p_budget=None):
     """Fit pLSA with k topics to the sparse doc-term matrix X; returns (P(z|d) [n,k], P(w|z) [k,m]),
     both float32 (plsa.py:643-730).  Extra keyword arguments select the device, the kernel
     schedule (fused / materialised) and the arithmetic (`arithmetic="reference"`: the reference's float32 sums,
-    rounding for rounding -- engine.arithmetic_flags); positional compatibility is unchanged."""
+    rounding for rounding -- engine.arithmetic_flags); positional compatibility is unchanged.
+    p_budget: bytes that P(z|w,d) may take in the reference arithmetic (None: ENSTOP_AMD_P_BUDGET_MB, unset: no budget) --
+    the documents are then walked in blocks that fit, with the same bits; no effect outside the reference arithmetic."""
     if not issparse(X):
         X = csr_matrix(X)
     eng = get_engine(device)
     eng.upload_csr(X)
     if arithmetic is not None:
         flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
-    iters, ll = _fit_on_engine(eng, k, sample_weight, init, n_iter, n_iter_per_test, tolerance,
-                               e_step_thresh, random_state, flags, trace=return_info, X_for_init=X)
+    with _PBudget(eng, p_budget):
+        iters, ll = _fit_on_engine(eng, k, sample_weight, init, n_iter, n_iter_per_test, tolerance,
+                                   e_step_thresh, random_state, flags, trace=return_info, X_for_init=X)
     p_z_given_d, p_w_given_z = eng.get_factors()
     if return_info:
         return p_z_given_d, p_w_given_z, dict(n_iter=iters, log_likelihood_trace=ll)
@@ -318,8 +344,10 @@ def plsa_refit_inner(X_rows, X_cols, X_vals, topics, p_z_given_d, sample_weight,
 
 @_locked
 def plsa_refit(X, topics, sample_weight, n_iter=50, n_iter_per_test=10, tolerance=0.005,
-               e_step_thresh=1e-32, random_state=None, device=None, flags=None, return_info=False, arithmetic=None):
-    """Document vectors P(z|d) for X against fixed `topics` (plsa.py:923-997)."""
+               e_step_thresh=1e-32, random_state=None, device=None, flags=None, return_info=False, arithmetic=None,
+               p_budget=None):
+    """Document vectors P(z|d) for X against fixed `topics` (plsa.py:923-997).  p_budget: as in plsa_fit (bytes for
+    P(z|w,d) in the reference arithmetic; no effect outside it)."""
     if arithmetic is not None:
         flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
     if not issparse(X):
@@ -343,7 +371,8 @@ def plsa_refit(X, topics, sample_weight, n_iter=50, n_iter_per_test=10, toleranc
     sw = None
     if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
         sw = np.asarray(sample_weight, np.float32)
-    iters, ll = eng.refit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=return_info)
+    with _PBudget(eng, p_budget):
+        iters, ll = eng.refit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=return_info)
     U, _ = eng.get_factors(want_v=False)
     if return_info:
         return U, dict(n_iter=iters, log_likelihood_trace=ll)
@@ -378,6 +407,9 @@ class PLSA(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
     `embedding_` = P(z|d) [n, k], `training_data_`.  Additive: `n_iter_` (EM iterations run),
     and the `device` constructor keyword at the end of the signature.
 
+    `p_budget`: bytes that P(z|w,d) may take in fit / transform with `arithmetic="reference"` (plsa_fit; None: the
+    ENSTOP_AMD_P_BUDGET_MB environment variable, unset: no budget); no effect outside the reference arithmetic.
+
     Conscious deviations from reference defects: float input detection works on
     current NumPy (the reference's `np.float` raises); `sample_weight` is restricted to the
     non-empty rows together with the data (the reference leaves it misaligned, plsa.py:1144-1164).
@@ -385,9 +417,10 @@ class PLSA(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
 
     def __init__(self, n_components=10, init="random", n_iter=100, n_iter_per_test=10,
                  tolerance=0.001, e_step_thresh=1e-32, transform_random_seed=42, random_state=None,
-                 device=None, arithmetic=None):
+                 device=None, arithmetic=None, p_budget=None):
         self.n_components = n_components
         self.arithmetic = arithmetic
+        self.p_budget = p_budget
         self.init = init
         self.n_iter = n_iter
         self.n_iter_per_test = n_iter_per_test
@@ -406,7 +439,7 @@ class PLSA(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
     def _fit_factors(self, X, sample_weight):
         return plsa_fit(X, self.n_components, sample_weight, self.init, self.n_iter, self.n_iter_per_test,
                         self.tolerance, self.e_step_thresh, self.random_state, device=self.device,
-                        flags=self._flags(), return_info=True)
+                        flags=self._flags(), return_info=True, p_budget=getattr(self, "p_budget", None))
 
     def fit(self, X, y=None, sample_weight=None):
         self.fit_transform(X, sample_weight=sample_weight)
@@ -446,7 +479,7 @@ class PLSA(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
         # plsa.py:1210-1218: fixed n_iter=50, n_iter_per_test=5, tolerance=0.001
         return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5,
                           tolerance=0.001, random_state=random_state, device=self.device,
-                          flags=self._flags())
+                          flags=self._flags(), p_budget=getattr(self, "p_budget", None))
 
 
 class StreamedPLSA(PLSA):
@@ -480,7 +513,7 @@ class StreamedPLSA(PLSA):
         X = csr_matrix(X) if not issparse(X) else X.tocsr()
         return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5,
                           tolerance=0.001, random_state=random_state, device=self.device,
-                          flags=self._flags())
+                          flags=self._flags(), p_budget=getattr(self, "p_budget", None))
 
 
 class BlockParallelPLSA(PLSA):

@@ -52,7 +52,9 @@ enum {
                            arithmetic at 3 M non-zeros.  Results are the bits of the reference's source executed statement by
                            statement (the fixtures under tests/golden; the numba-compiled reference sits 2e-5 from them at config 1).  The
                            kernel sequence is the reference's (P(z|w,d) materialised; PLSA_FUSED is ignored); a parity mode, 20-110 ms
-                           per iteration at the BASELINE sizes, not available with PLSA_SHARDED.  The log-likelihood stays the
+                           per iteration at the BASELINE sizes, not available with PLSA_SHARDED.  P(z|w,d) is one array for all
+                           non-zeros unless plsa_set_p_budget (plsa_hip_blocked.h) bounds it: the drivers then walk the documents
+                           in blocks that fit, every chain handed from block to block -- the same bits.  The log-likelihood stays the
                            float64-accumulated one (which is what the compiled reference's vectorised reduction delivers to 1e-7) unless: */
     PLSA_REFERENCE_LL = 512, /* the log-likelihood as ONE float32 running sum over the non-zeros in COO order, its inner product a float32
                            sum over the topics in order (enstop/plsa.py:322, 378-384 read literally: one thread, no SIMD).  3.4e-3 from
