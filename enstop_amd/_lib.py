@@ -1,5 +1,5 @@
-"""ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h and
-plsa_hip_metrics.h).
+"""ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h,
+plsa_hip_metrics.h, plsa_hip_blocked.h and plsa_hip_embed.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -136,6 +136,12 @@ BLOCKED_SIGNATURES = {
     "plsa_p_block_info": (C.c_int, [_ctx, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
+# include/plsa_hip_embed.h: the native embedding of topic_combination="hellinger_umap" (its own table as well)
+EMBED_SIGNATURES = {
+    "plsa_knn_membership": (C.c_int, [_ctx, _f64p, _i64, _i32, _i32p, _f32p, _f32p, _f32p, _f32p]),
+    "plsa_layout": (C.c_int, [_ctx, _i32p, _i32p, _f32p, _i64, _i32, _f32p, _i32, C.c_float, C.c_float, _i32, C.c_uint64, _i32]),
+}
+
 _lib = None
 HW_QUEUES = {"set_by": None, "hip_mapped_before_load": None}
 
@@ -186,7 +192,7 @@ def load():
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
-            list(BLOCKED_SIGNATURES.items()):
+            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -10,7 +10,8 @@ DEPS = [SRC, os.path.join(HERE, "csrc", "plsa_kernels.hpp"), os.path.join(HERE, 
         os.path.join(HERE, "csrc", "plsa_synth.hpp"), os.path.join(HERE, "csrc", "mt_jump.hpp"),
         os.path.join(os.path.dirname(HERE), "include", "plsa_hip.h"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_diag.h"),
         os.path.join(HERE, "csrc", "plsa_metric_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_metrics.h"),
-        os.path.join(os.path.dirname(HERE), "include", "plsa_hip_blocked.h")]
+        os.path.join(os.path.dirname(HERE), "include", "plsa_hip_blocked.h"),
+        os.path.join(HERE, "csrc", "plsa_embed_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_embed.h")]
 OUT = os.path.join(HERE, "libplsa_hip.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))

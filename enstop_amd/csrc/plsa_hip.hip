@@ -34,7 +34,9 @@
 #include "../../include/plsa_hip_members.h"
 #include "../../include/plsa_hip_metrics.h"
 #include "../../include/plsa_hip_blocked.h"
+#include "../../include/plsa_hip_embed.h"
 #include "mt_jump.hpp"
+#include "plsa_embed_kernels.hpp"
 #include "plsa_kernels.hpp"
 #include "plsa_member_kernels.hpp"
 #include "plsa_metric_kernels.hpp"
@@ -3411,6 +3413,141 @@ int plsa_codocument_counts(plsa_ctx *c, const int32_t *words, int64_t sets, int3
         HIPCHK(c, hipMemcpyAsync(positive + s0 * nw, d_pos, sizeof(int64_t) * (size_t)(cs * nw), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // the next chunk reuses the staging buffers
     }
+    return 0;
+}
+
+// enstop/enstop_.py:354-414 (umap.UMAP on the stacked topics): nearest neighbours, bandwidths and membership strengths of a
+// precomputed distance matrix -- plsa_embed_kernels.hpp
+int plsa_knn_membership(plsa_ctx *c, const double *D, int64_t t, int32_t n_neighbors, int32_t *idx, float *dist, float *rho,
+                        float *sigma, float *member) {
+    if (!c) return fail(c, "plsa_knn_membership: ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!D || !idx || !dist || !rho || !sigma || !member) return fail(c, "plsa_knn_membership: an array is NULL");
+    if (t < 2 || t > 65536) return fail(c, "plsa_knn_membership: t=%lld outside [2,65536]", (long long)t);
+    if (n_neighbors < 1 || n_neighbors > t || n_neighbors > plsa::EMBED_MAX_NEIGHBORS)
+        return fail(c, "plsa_knn_membership: n_neighbors=%d outside [1,min(t,%d)]", n_neighbors, plsa::EMBED_MAX_NEIGHBORS);
+    for (i64 i = 0; i < t * t; ++i)      // a NaN would never be selected: a row could run out of entries
+        if (!std::isfinite(D[i])) return fail(c, "plsa_knn_membership: D[%lld,%lld] is not finite", (long long)(i / t), (long long)(i % t));
+    const size_t tk = (size_t)t * (size_t)n_neighbors;
+    DevBuf dD, dint, dflt;
+    CHK(ensure(c, dD, sizeof(double) * (size_t)t * t));
+    CHK(ensure(c, dint, sizeof(int) * (tk + 1)));                     // idx, the arrival counter
+    CHK(ensure(c, dflt, sizeof(float) * (2 * tk + 3 * (size_t)t)));   // dist, member, rho, sigma, row sums
+    int *d_idx = dint.as<int>();
+    unsigned *d_done = reinterpret_cast<unsigned *>(d_idx + tk);
+    float *d_dist = dflt.as<float>(), *d_member = d_dist + tk, *d_rho = d_member + tk, *d_sigma = d_rho + t, *d_sum = d_sigma + t;
+    HIPCHK(c, hipMemcpyAsync(dD.p, D, sizeof(double) * (size_t)t * t, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_done, 0, sizeof(unsigned), c->stream));
+    { Scope s(c, "k_knn_membership");
+      hipLaunchKernelGGL(plsa::k_knn_membership, dim3((unsigned)t), dim3(64), 0, c->stream, dD.as<double>(), (int)t, (int)n_neighbors,
+                         d_idx, d_dist, d_rho, d_sigma, d_member, d_sum, d_done); }
+    CHK(launch_check(c, "k_knn_membership"));
+    HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * tk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dist, d_dist, sizeof(float) * tk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(member, d_member, sizeof(float) * tk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rho, d_rho, sizeof(float) * (size_t)t, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sigma, d_sigma, sizeof(float) * (size_t)t, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C++" {
+namespace {
+template <int DIM>
+int layout_run(plsa_ctx *c, const plsa::LayoutGraph &G, float *y0, float *y1, bool lds, float **result) {
+    if (lds) {
+        { Scope s(c, "k_layout_lds");
+          hipLaunchKernelGGL(plsa::k_layout_lds<DIM>, dim3(1), dim3(plsa::LAYOUT_LDS_BLOCK), sizeof(float) * 2 * (size_t)G.t * DIM,
+                             c->stream, G, y0); }
+        *result = y0;
+        return launch_check(c, "k_layout_lds");
+    }
+    const unsigned grid = (unsigned)((G.t + plsa::LAYOUT_EPOCH_BLOCK - 1) / plsa::LAYOUT_EPOCH_BLOCK);
+    float *cur = y0, *nxt = y1;
+    for (int epoch = 0; epoch < G.n_epochs; ++epoch) {
+        { Scope s(c, "k_layout_epoch");
+          hipLaunchKernelGGL(plsa::k_layout_epoch<DIM>, dim3(grid), dim3(plsa::LAYOUT_EPOCH_BLOCK), 0, c->stream, G, epoch, cur, nxt); }
+        CHK(launch_check(c, "k_layout_epoch"));
+        std::swap(cur, nxt);
+    }
+    *result = cur;
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+// enstop/enstop_.py:354-414 (umap.UMAP on the stacked topics): the force layout of the fuzzy graph -- plsa_embed_kernels.hpp
+int plsa_layout(plsa_ctx *c, const int32_t *indptr, const int32_t *indices, const float *weights, int64_t t, int32_t dim,
+                float *y_inout, int32_t n_epochs, float a, float b, int32_t negative_sample_rate, uint64_t seed, int32_t path) {
+    if (!c) return fail(c, "plsa_layout: ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!indptr || !y_inout) return fail(c, "plsa_layout: indptr and y_inout must not be NULL");
+    if (t < 1 || t > 65536) return fail(c, "plsa_layout: t=%lld outside [1,65536]", (long long)t);
+    if (dim < 1 || dim > plsa::EMBED_MAX_DIM) return fail(c, "plsa_layout: dim=%d outside [1,%d]", dim, plsa::EMBED_MAX_DIM);
+    if (n_epochs < 1 || n_epochs > 100000) return fail(c, "plsa_layout: n_epochs=%d outside [1,100000]", n_epochs);
+    if (negative_sample_rate < 1 || negative_sample_rate > 64)
+        return fail(c, "plsa_layout: negative_sample_rate=%d outside [1,64]", negative_sample_rate);
+    if (path < 0 || path > 2) return fail(c, "plsa_layout: path=%d is none of 0 (auto), 1 (LDS), 2 (per epoch)", path);
+    if (!std::isfinite(a) || !std::isfinite(b) || a <= 0.f || b <= 0.f) return fail(c, "plsa_layout: a and b must be positive");
+    // the graph indexes the position buffers on the device: checked here, before anything is launched
+    if (indptr[0] != 0) return fail(c, "plsa_layout: indptr[0] is not 0");
+    for (i64 i = 0; i < t; ++i)
+        if (indptr[i + 1] < indptr[i]) return fail(c, "plsa_layout: indptr decreases at row %lld", (long long)i);
+    const i64 nnz = indptr[t];
+    if (nnz > 0 && (!indices || !weights)) return fail(c, "plsa_layout: indices and weights must not be NULL");
+    float wmax = 0.f;
+    for (i64 e = 0; e < nnz; ++e) {
+        if (indices[e] < 0 || indices[e] >= t) return fail(c, "plsa_layout: indices[%lld]=%d outside [0,%lld)", (long long)e, indices[e], (long long)t);
+        if (!std::isfinite(weights[e]) || !(weights[e] > 0.f)) return fail(c, "plsa_layout: weights[%lld] is not a positive number", (long long)e);
+        wmax = std::max(wmax, weights[e]);
+    }
+    for (i64 i = 0; i < t * dim; ++i)
+        if (!std::isfinite(y_inout[i])) return fail(c, "plsa_layout: y_inout[%lld] is not finite", (long long)i);
+    const size_t y_bytes = sizeof(float) * (size_t)t * (size_t)dim;
+    const bool fits = 2 * y_bytes <= plsa::LAYOUT_LDS_BYTES;
+    if (path == 1 && !fits)
+        return fail(c, "plsa_layout: path 1 keeps two position buffers in LDS: 2 * %lld * %d * 4 = %zu bytes exceed %zu", (long long)t,
+                    dim, 2 * y_bytes, plsa::LAYOUT_LDS_BYTES);
+    const bool lds = path == 1 || (path == 0 && fits);
+    // the schedule in float32, as the kernels advance it: an edge is due every max(W) / w epochs, first in that epoch
+    const float rate = (float)negative_sample_rate;
+    std::vector<float> eps((size_t)nnz);
+    std::vector<float2> state((size_t)nnz);
+    for (i64 e = 0; e < nnz; ++e) {
+        eps[e] = wmax / weights[e];
+        state[e] = make_float2(eps[e], eps[e] / rate);
+    }
+    DevBuf dptr, dind, deps, dstate, dy;
+    CHK(ensure(c, dptr, sizeof(int) * (size_t)(t + 1)));
+    CHK(ensure(c, dind, sizeof(int) * (size_t)nnz));
+    CHK(ensure(c, deps, sizeof(float) * (size_t)nnz));
+    CHK(ensure(c, dstate, sizeof(float2) * (size_t)nnz));
+    CHK(ensure(c, dy, 2 * y_bytes));
+    HIPCHK(c, hipMemcpyAsync(dptr.p, indptr, sizeof(int) * (size_t)(t + 1), hipMemcpyHostToDevice, c->stream));
+    if (nnz > 0) {
+        HIPCHK(c, hipMemcpyAsync(dind.p, indices, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(deps.p, eps.data(), sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dstate.p, state.data(), sizeof(float2) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(dy.p, y_inout, y_bytes, hipMemcpyHostToDevice, c->stream));
+    plsa::LayoutGraph G;
+    G.indptr = dptr.as<int>(); G.indices = dind.as<int>(); G.eps = deps.as<float>(); G.state = dstate.as<float2>();
+    G.t = (int)t; G.n_epochs = n_epochs; G.a = a; G.b = b; G.rate = rate; G.seed = seed;
+    float *y0 = dy.as<float>(), *y1 = y0 + (size_t)t * dim, *result = nullptr;
+    int rc = 1;
+    switch (dim) {
+    case 1: rc = layout_run<1>(c, G, y0, y1, lds, &result); break;
+    case 2: rc = layout_run<2>(c, G, y0, y1, lds, &result); break;
+    case 3: rc = layout_run<3>(c, G, y0, y1, lds, &result); break;
+    case 4: rc = layout_run<4>(c, G, y0, y1, lds, &result); break;
+    case 5: rc = layout_run<5>(c, G, y0, y1, lds, &result); break;
+    case 6: rc = layout_run<6>(c, G, y0, y1, lds, &result); break;
+    case 7: rc = layout_run<7>(c, G, y0, y1, lds, &result); break;
+    case 8: rc = layout_run<8>(c, G, y0, y1, lds, &result); break;
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }   // the host vectors above are still being read
+    HIPCHK(c, hipMemcpyAsync(y_inout, result, y_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

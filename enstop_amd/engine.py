@@ -472,6 +472,76 @@ class Engine:
                                                 positive.reshape(-1)))
         return co, positive
 
+    # -- the embedding of topic_combination="hellinger_umap" (include/plsa_hip_embed.h; enstop_.py:354-414) ------------
+    def knn_membership(self, D, n_neighbors):
+        """Nearest neighbours, bandwidths and directed membership strengths of a precomputed distance matrix D [t, t]
+        (UMAP's first stage), one kernel launch.  n_neighbors counts the row's own entry and is capped at t - 1.
+        -> (idx [t, k] int32: the k smallest entries of each row, ascending, ties towards the lower column;
+        dist [t, k] float32; rho [t]; sigma [t]; member [t, k] float32)."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.ndim != 2 or D.shape[0] != D.shape[1]:
+            raise ValueError("D must be a square distance matrix")
+        t = D.shape[0]
+        if t < 2:
+            raise ValueError("an embedding needs at least 2 points, got %d" % t)
+        if int(n_neighbors) < 1:
+            raise ValueError("n_neighbors must be at least 1")
+        k = min(int(n_neighbors), t - 1)
+        idx = np.empty((t, k), np.int32)
+        dist, member = np.empty((t, k), np.float32), np.empty((t, k), np.float32)
+        rho, sigma = np.empty(t, np.float32), np.empty(t, np.float32)
+        self._ok(self._L.plsa_knn_membership(self._h, D.reshape(-1), t, k, idx.reshape(-1), dist.reshape(-1), rho, sigma,
+                                             member.reshape(-1)))
+        return idx, dist, rho, sigma, member
+
+    _LAYOUT_PATHS = {"auto": 0, "lds": 1, "epoch": 2, 0: 0, 1: 1, 2: 2}
+    last_layout_path = None        # layout: "lds" | "epoch"
+    last_embedding_info = None     # hellinger_embedding
+
+    def layout(self, W_csr, init, n_epochs=None, a=None, b=None, negative_sample_rate=5, seed=0, path="auto"):
+        """The force layout of the symmetric fuzzy graph W_csr [t, t] from the positions init [t, dim]: synchronous and
+        deterministic (every vertex reads the epoch's starting positions and moves once), a function of the inputs and
+        `seed`.  n_epochs: 500 up to 10 000 vertices, else 200; a, b: from min_dist = 0.1, spread = 1.
+        path: "auto" | "lds" (1: one persistent workgroup, positions in LDS; DeviceError when 2 * t * dim * 4 bytes exceed
+        64 KiB) | "epoch" (2: one launch per epoch); both give the same bits.  -> [t, dim] float32; the path taken is in
+        `last_layout_path`."""
+        from . import embedding
+        import scipy.sparse as sp
+        W = sp.csr_matrix(W_csr)
+        W.sort_indices()
+        Y = np.array(init, dtype=np.float32, order="C", copy=True)
+        if Y.ndim != 2 or W.shape != (Y.shape[0], Y.shape[0]):
+            raise ValueError("init must be [t, dim] for a [t, t] graph")
+        t, dim = Y.shape
+        if path not in self._LAYOUT_PATHS:
+            raise ValueError('path must be "auto", "lds" (1) or "epoch" (2)')
+        if a is None or b is None:
+            a, b = embedding.find_ab_params()
+        n_epochs = embedding.default_n_epochs(t) if n_epochs is None else int(n_epochs)
+        code = self._LAYOUT_PATHS[path]
+        self._ok(self._L.plsa_layout(self._h, np.ascontiguousarray(W.indptr, np.int32), np.ascontiguousarray(W.indices, np.int32),
+                                     np.ascontiguousarray(W.data, np.float32), t, dim, Y.reshape(-1), n_epochs, float(a), float(b),
+                                     int(negative_sample_rate), int(seed) & 0xFFFFFFFFFFFFFFFF, code))
+        self.last_layout_path = "epoch" if code == 2 or (code == 0 and 2 * t * dim * 4 > 65536) else "lds"
+        return Y
+
+    def hellinger_embedding(self, topics, n_neighbors=15, n_components=5, seed=0):
+        """UMAP of the rows of `topics` [t, m] under the Hellinger distance, natively (enstop_.py:354-414 calls
+        umap.UMAP(n_neighbors, n_components, metric="hellinger")): all_pairs_hellinger -> knn_membership -> the symmetric
+        fuzzy graph, its schedule and the initial layout on the host (embedding.py) -> layout.  -> [t, n_components]
+        float32; `last_embedding_info` says what was done."""
+        from . import embedding
+        D = self.all_pairs_hellinger(topics)
+        t = D.shape[0]
+        idx, _, _, _, member = self.knn_membership(D, n_neighbors)
+        n_epochs = embedding.default_n_epochs(t)
+        W = embedding.prune_for_schedule(embedding.fuzzy_graph(idx, member), n_epochs)
+        Y0, init, components = embedding.initial_layout(W, int(n_components), seed)
+        Y = self.layout(W, Y0, n_epochs=n_epochs, negative_sample_rate=embedding.NEGATIVE_SAMPLE_RATE, seed=seed)
+        self.last_embedding_info = dict(t=t, n_neighbors=idx.shape[1], components=components, init=init, n_epochs=n_epochs,
+                                        edges=int(W.nnz), path=self.last_layout_path)
+        return Y
+
     def reference_chain_info(self):
         """norm_pwz of the reference arithmetic (plsa_reference_chain_info): chunks of the parity-pair walk that took the slow way,
         chunks walked, and whether this context is on the serial chain for the current corpus."""

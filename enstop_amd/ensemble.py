@@ -15,8 +15,9 @@ neither is installable in the build image.  The HDBSCAN* tree step is the produc
 (`hdbscan_tree.py`: Prim order, interval dendrogram, leaf clusters, hdbscan's conventions for core
 distances and cluster numbering) for "kl_divergence" and "hellinger", checked against a restatement of
 hdbscan's published routines and against scikit-learn's public estimator (tests/test_hdbscan_tree.py);
-no private scikit-learn module is imported.  "hellinger_umap" needs
-`umap-learn` and raises ImportError when it is absent.  The all-pairs Hellinger matrix follows
+no private scikit-learn module is imported.  "hellinger_umap" embeds natively when it is
+given an engine (`Engine.hellinger_embedding`: UMAP as published, not a run of umap-learn) and
+needs `umap-learn` without one, raising ImportError when it is absent.  The all-pairs Hellinger matrix follows
 umap.distances.hellinger's published definition (umap-learn >= 0.3.8) and is checked against that
 definition, not against a reference run.
 
@@ -132,15 +133,29 @@ def generate_combined_topics_hellinger(all_topics, min_samples=5, min_cluster_si
 
 
 def generate_combined_topics_hellinger_umap(all_topics, min_samples=5, min_cluster_size=5,
-                                            n_neighbors=15, reduced_dim=5, engine=None):
-    try:
-        import umap
-    except ImportError as e:
-        raise ImportError('topic_combination="hellinger_umap" needs the umap-learn package; '
-                          'use topic_combination="hellinger" instead') from e
+                                            n_neighbors=15, reduced_dim=5, engine=None, random_state=None):
+    """enstop_.py:354-414.  With `engine` (how `ensemble_fit` calls it) the embedding is the native one,
+    `Engine.hellinger_embedding`: UMAP as published on the device's exact Hellinger matrix, with a synchronous,
+    deterministic layout seeded by `random_state` (0 when None) -- a stream of its own, nothing is drawn from the
+    estimator's.  ENSTOP_AMD_EMBEDDING=umap-learn sends it to the umap-learn package instead (A/B where it exists).
+    Without an engine the package is the only path, and its absence is an ImportError: there is no host embedding."""
+    import os
+    choice = os.environ.get("ENSTOP_AMD_EMBEDDING", "native")
+    if choice not in ("native", "umap-learn"):
+        raise ValueError('ENSTOP_AMD_EMBEDDING=%r: expected "native" or "umap-learn"' % (choice,))
     from sklearn.cluster import HDBSCAN
-    embedding = umap.UMAP(n_neighbors=n_neighbors, n_components=reduced_dim,
-                          metric="hellinger").fit_transform(all_topics)
+    if engine is not None and choice == "native":
+        seed = 0 if random_state is None else int(random_state)
+        embedding = np.asarray(engine.hellinger_embedding(all_topics, n_neighbors=n_neighbors, n_components=reduced_dim,
+                                                          seed=seed), dtype=np.float64)
+    else:
+        try:
+            import umap
+        except ImportError as e:
+            raise ImportError('topic_combination="hellinger_umap" needs the umap-learn package; '
+                              'use topic_combination="hellinger" instead') from e
+        embedding = umap.UMAP(n_neighbors=n_neighbors, n_components=reduced_dim,
+                              metric="hellinger").fit_transform(all_topics)
     # scikit-learn's public estimator on the embedding; its min_samples counts the point itself, hdbscan's
     # (enstop_.py:388-392) does not: + 1 gives the same core distances
     clusterer = HDBSCAN(min_samples=min_samples + 1, min_cluster_size=min_cluster_size,
@@ -174,8 +189,11 @@ def ensemble_fit(X, estimated_n_topics=10, model="plsa", init="random", min_samp
                                     random_state=random_state, device=device,
                                     **(dict(beta_loss=beta_loss, alpha=alpha, solver=solver) if model == "nmf" else {}))
     from .engine import get_engine
+    extra = {}
+    if topic_combination == "hellinger_umap" and isinstance(random_state, (int, np.integer)):
+        extra["random_state"] = int(random_state)          # the layout's own stream: nothing is drawn from random_state
     stable_topics = _topic_combiner[topic_combination](all_topics, min_samples, min_cluster_size,
-                                                       engine=get_engine(device))
+                                                       engine=get_engine(device), **extra)
     if stable_topics.shape[0] == 0:
         raise ValueError("topic combination found no stable topic cluster; lower min_samples / "
                          "min_cluster_size or raise n_starts")
