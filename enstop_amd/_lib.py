@@ -1,5 +1,5 @@
 """ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h,
-plsa_hip_metrics.h, plsa_hip_blocked.h and plsa_hip_embed.h).
+plsa_hip_metrics.h, plsa_hip_blocked.h, plsa_hip_embed.h and plsa_hip_nmf.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -142,6 +142,16 @@ EMBED_SIGNATURES = {
     "plsa_layout": (C.c_int, [_ctx, _i32p, _i32p, _f32p, _i64, _i32, _f32p, _i32, C.c_float, C.c_float, _i32, C.c_uint64, _i32]),
 }
 
+# include/plsa_hip_nmf.h: Kullback-Leibler NMF by multiplicative updates (its own table as well)
+NMF_SIGNATURES = {
+    "plsa_nmf_set_factors": (C.c_int, [_ctx, _f32p, _f32p, _i64, _i64, _i32]),
+    "plsa_nmf_get_factors": (C.c_int, [_ctx, _vp, _vp]),
+    "plsa_nmf_update_w": (C.c_int, [_ctx]),
+    "plsa_nmf_update_h": (C.c_int, [_ctx]),
+    "plsa_nmf_divergence": (C.c_int, [_ctx, C.POINTER(C.c_double)]),
+    "plsa_nmf_fit": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.POINTER(_i32), _vp, _i32]),
+}
+
 _lib = None
 HW_QUEUES = {"set_by": None, "hip_mapped_before_load": None}
 
@@ -192,7 +202,7 @@ def load():
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
-            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()):
+            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -11,7 +11,9 @@ DEPS = [SRC, os.path.join(HERE, "csrc", "plsa_kernels.hpp"), os.path.join(HERE, 
         os.path.join(os.path.dirname(HERE), "include", "plsa_hip.h"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_diag.h"),
         os.path.join(HERE, "csrc", "plsa_metric_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_metrics.h"),
         os.path.join(os.path.dirname(HERE), "include", "plsa_hip_blocked.h"),
-        os.path.join(HERE, "csrc", "plsa_embed_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_embed.h")]
+        os.path.join(HERE, "csrc", "plsa_embed_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_embed.h"),
+        os.path.join(HERE, "csrc", "plsa_nmf_kernels.hpp"), os.path.join(HERE, "csrc", "plsa_nmf.hpp"),
+        os.path.join(os.path.dirname(HERE), "include", "plsa_hip_nmf.h")]
 OUT = os.path.join(HERE, "libplsa_hip.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))

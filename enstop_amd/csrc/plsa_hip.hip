@@ -35,11 +35,13 @@
 #include "../../include/plsa_hip_metrics.h"
 #include "../../include/plsa_hip_blocked.h"
 #include "../../include/plsa_hip_embed.h"
+#include "../../include/plsa_hip_nmf.h"
 #include "mt_jump.hpp"
 #include "plsa_embed_kernels.hpp"
 #include "plsa_kernels.hpp"
 #include "plsa_member_kernels.hpp"
 #include "plsa_metric_kernels.hpp"
+#include "plsa_nmf_kernels.hpp"
 #include "plsa_ref_kernels.hpp"
 #include "plsa_synth.hpp"
 
@@ -254,6 +256,9 @@ struct plsa_ctx {
     // plsa_codocument_counts: one 32-bit mask per document and set of a chunk; the chunk's word lists and counters.  Kept
     // between calls (a sweep scores one model after the other), freed by plsa_release_scratch
     DevBuf metric_mask, metric_small;
+    // KL-divergence NMF (plsa_nmf.hpp): W_sum / H_sum as float64 [2][kp] and guarded float32 [2][kp], the slab sums they are
+    // added up from, the objective's per-workgroup partials and its result.  W and H themselves live in U[cu] / Vt[cv]
+    struct Nmf { DevBuf raw, guarded, slabs, obj, out; } nmf;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -3778,3 +3783,4 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 }  // extern "C"
 
 #include "plsa_members.hpp"   // batched ensemble members (include/plsa_hip_members.h)
+#include "plsa_nmf.hpp"       // KL-divergence NMF (include/plsa_hip_nmf.h)

@@ -246,6 +246,48 @@ class Engine:
     def copy_components_to_device(self, device_ptr):
         self._ok(self._L.plsa_copy_components_to_device(self._h, int(device_ptr)))
 
+    # -- KL-divergence NMF (include/plsa_hip_nmf.h) --------------------------------------------------
+    def nmf_set_factors(self, W, H):
+        W, H = _f32(W), _f32(H)
+        n, k = W.shape
+        _, m, _ = self.shape
+        if H.shape != (k, m):
+            raise ValueError("H has shape %s, expected %s" % (H.shape, (k, m)))
+        self._ok(self._L.plsa_nmf_set_factors(self._h, W, H, n, m, k))
+        self.k = k
+        return self
+
+    def nmf_get_factors(self, want_w=True, want_h=True):
+        n, m, _ = self.shape
+        W = np.empty((n, self.k), np.float32) if want_w else None
+        H = np.empty((self.k, m), np.float32) if want_h else None
+        self._ok(self._L.plsa_nmf_get_factors(self._h, ptr(W), ptr(H)))
+        return W, H
+
+    def nmf_update_w(self):
+        self._ok(self._L.plsa_nmf_update_w(self._h))
+        return self
+
+    def nmf_update_h(self):
+        self._ok(self._L.plsa_nmf_update_h(self._h))
+        return self
+
+    def nmf_divergence(self):
+        """sqrt(2 D), D the generalised Kullback-Leibler divergence of the active matrix from W H"""
+        out = C.c_double(0.0)
+        self._ok(self._L.plsa_nmf_divergence(self._h, C.byref(out)))
+        return out.value
+
+    def nmf_fit(self, update_h=True, max_iter=200, tol=1e-4):
+        """(n_iter, errors): errors[0] is the objective before the first update, then one entry per stopping test"""
+        max_iter = int(max_iter)
+        errors = np.zeros(max(max_iter, 0) // 10 + 2, np.float64)
+        n_iter = C.c_int32(0)
+        self._ok(self._L.plsa_nmf_fit(self._h, 1 if update_h else 0, max_iter, float(tol), C.byref(n_iter), ptr(errors),
+                                      errors.shape[0]))
+        tested = n_iter.value // 10 if tol > 0 else 0
+        return n_iter.value, errors[:1 + tested].copy()
+
     # -- kernel-level operators --------------------------------------------------------------------
     def set_arithmetic(self, arithmetic=None):
         """Arithmetic of e_step / m_step / log_likelihood and of later fits on this engine (arithmetic_flags)."""

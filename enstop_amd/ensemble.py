@@ -174,7 +174,7 @@ def ensemble_fit(X, estimated_n_topics=10, model="plsa", init="random", min_samp
                  min_cluster_size=4, n_starts=16, n_jobs=1, parallelism="dask",
                  topic_combination="hellinger_umap", bootstrap=True, n_iter=100, n_iter_per_test=10,
                  tolerance=0.001, e_step_thresh=1e-16, lift_factor=1, beta_loss=1, alpha=0.0,
-                 solver="mu", random_state=None, device=None):
+                 solver="mu", random_state=None, device=None, nmf_backend=None):
     """Stable topics from an ensemble of bootstrapped pLSA fits, then document vectors against them
     (enstop_.py:417-584).  Returns (doc_vectors [n_docs, M], stable_topics [M, n_words])."""
     if model not in ("plsa", "nmf"):
@@ -187,7 +187,8 @@ def ensemble_fit(X, estimated_n_topics=10, model="plsa", init="random", min_samp
                                     init=init, n_iter=n_iter, n_iter_per_test=n_iter_per_test,
                                     tolerance=tolerance, e_step_thresh=e_step_thresh, bootstrap=bootstrap,
                                     random_state=random_state, device=device,
-                                    **(dict(beta_loss=beta_loss, alpha=alpha, solver=solver) if model == "nmf" else {}))
+                                    **(dict(beta_loss=beta_loss, alpha=alpha, solver=solver, nmf_backend=nmf_backend)
+                                       if model == "nmf" else {}))
     from .engine import get_engine
     extra = {}
     if topic_combination == "hellinger_umap" and isinstance(random_state, (int, np.integer)):
@@ -200,7 +201,14 @@ def ensemble_fit(X, estimated_n_topics=10, model="plsa", init="random", min_samp
     if lift_factor != 1:
         stable_topics = stable_topics.astype(np.float64) ** lift_factor
         stable_topics = (stable_topics / stable_topics.sum(axis=1, keepdims=True)).astype(np.float32)
-    if model == "nmf":                          # enstop_.py:570-579, host scikit-learn like the reference
+    if model == "nmf":                          # enstop_.py:570-579: scikit-learn on the host like the reference, or nmf_refit
+        from . import enstop_, nmf as _nmf
+        # (the refit starts from a constant W: no init to choose)
+        if _nmf.use_device(nmf_backend, device, init="nndsvd", beta_loss=beta_loss, solver=solver, alpha=alpha):
+            doc_vectors, _ = _nmf.nmf_refit(X, stable_topics, device=device)
+            enstop_.last_nmf_path = "device"
+            return doc_vectors, stable_topics
+        enstop_.last_nmf_path = "host"
         from sklearn.decomposition import non_negative_factorization
         doc_vectors, _, _ = non_negative_factorization(
             X, H=np.asarray(stable_topics, dtype=X.dtype), n_components=stable_topics.shape[0],
@@ -222,7 +230,7 @@ class EnsembleTopics(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
                  min_cluster_size=5, n_jobs=8, parallelism="dask", topic_combination="hellinger_umap",
                  bootstrap=True, n_iter=80, n_iter_per_test=10, tolerance=0.001, e_step_thresh=1e-32,
                  lift_factor=1, beta_loss=1, alpha=0.0, solver="mu", transform_random_seed=42,
-                 random_state=None, device=None):
+                 random_state=None, device=None, nmf_backend=None):
         self.n_components = n_components
         self.model = model
         self.init = init
@@ -244,6 +252,7 @@ class EnsembleTopics(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
         self.transform_random_seed = transform_random_seed
         self.random_state = random_state
         self.device = device
+        self.nmf_backend = nmf_backend
 
     def fit(self, X, y=None):
         self.fit_transform(X)
@@ -257,7 +266,8 @@ class EnsembleTopics(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
                             self.min_cluster_size, self.n_starts, self.n_jobs, self.parallelism,
                             self.topic_combination, self.bootstrap, self.n_iter, self.n_iter_per_test,
                             self.tolerance, self.e_step_thresh, self.lift_factor, self.beta_loss,
-                            self.alpha, self.solver, self.random_state, device=self.device)
+                            self.alpha, self.solver, self.random_state, device=self.device,
+                            nmf_backend=self.nmf_backend)
         self.components_ = V
         self.embedding_ = U
         self.training_data_ = X

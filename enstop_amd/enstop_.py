@@ -212,36 +212,102 @@ def plsa_topics(X, k, **kwargs):
         e_step_thresh=kwargs.get("e_step_thresh", 1e-16), flags=_member_flags(kwargs))
 
 
-def nmf_topics(X, k, **kwargs):
-    """enstop_.py:118-161: bootstrap-resample the documents, fit scikit-learn's NMF on the HOST, return
-    the L1-row-normalised components.  NMF is a different model from pLSA and not part of the GPU hot
-    path (SURVEY.md section 2 lists it out of scope); it is delegated to scikit-learn exactly as the
-    reference does so that `model="nmf"` keeps working.  `alpha` maps to `alpha_W` (scikit-learn
-    renamed the parameter in 1.0)."""
+last_nmf_path = None          # "host" / "device": where the last nmf_topics / ensemble member / NMF refit ran
+
+
+def _nmf_config(kwargs):
+    return dict(init=kwargs.get("init", "nndsvd"), beta_loss=kwargs.get("beta_loss", 1), solver=kwargs.get("solver", "mu"),
+                alpha=kwargs.get("alpha", 0.0))
+
+
+def _nmf_topics_host(A, k, kwargs):
     from sklearn.decomposition import NMF
-    from .utils import normalize
-    A = X.tocsr() if issparse(X) else csr_matrix(X)
     if kwargs.get("bootstrap", True):
         rng = check_random_state(kwargs.get("random_state", None))
         A = A[rng.randint(0, A.shape[0], size=A.shape[0])]
     nmf = NMF(n_components=k, init=kwargs.get("init", "nndsvd"), beta_loss=kwargs.get("beta_loss", 1),
               alpha_W=kwargs.get("alpha", 0.0), solver=kwargs.get("solver", "mu"),
               random_state=kwargs.get("random_state", None)).fit(A)
-    topics = np.array(nmf.components_, dtype=np.float64, order="C")
+    return nmf.components_
+
+
+def _nmf_topics_on_engine(eng, A, k, kwargs):
+    """One member on a corpus already uploaded to `eng`: the same bootstrap draw, resampled on the device; the starting
+    factors from the resampled matrix on the host (public APIs), the fit on the device."""
+    from . import nmf as _nmf
+    random_state = kwargs.get("random_state", None)
+    if kwargs.get("bootstrap", True):
+        rng = check_random_state(random_state)
+        idx = rng.randint(0, A.shape[0], size=A.shape[0])
+        eng.bootstrap(idx)
+        A = A[idx]
+    else:
+        eng.bootstrap(None)
+    W0, H0 = _nmf.nmf_init(A, k, kwargs.get("init", "nndsvd"), random_state)
+    _nmf.fit_on_engine(eng, W0, H0, True, 200, 1e-4)           # NMF's defaults: max_iter=200, tol=1e-4
+    _, H = eng.nmf_get_factors(want_w=False)
+    return H
+
+
+def nmf_topics(X, k, **kwargs):
+    """enstop_.py:118-161: bootstrap-resample the documents, fit NMF (Kullback-Leibler, multiplicative updates), return
+    the L1-row-normalised components.  `backend`: "host" (scikit-learn's NMF, exactly as the reference calls it; `alpha`
+    maps to `alpha_W`, scikit-learn renamed the parameter in 1.0), "device" (enstop_amd.nmf: the same arithmetic on the
+    GPU; ValueError for what it does not carry: another beta_loss / solver / init, alpha != 0) or None: ENSTOP_AMD_NMF =
+    host | device | auto, default host.  `last_nmf_path` says what ran."""
+    global last_nmf_path
+    from .utils import normalize
+    from . import nmf as _nmf
+    on_device = _nmf.use_device(kwargs.get("backend", None), kwargs.get("device", None), **_nmf_config(kwargs))
+    A = X.tocsr() if issparse(X) else csr_matrix(X)
+    if on_device:
+        eng = get_engine(kwargs.get("device", None))
+        with eng.lock:
+            A = A.astype(np.float32, copy=False)
+            eng.upload_csr(A)
+            try:
+                components = _nmf_topics_on_engine(eng, A, k, kwargs)
+            finally:
+                eng.bootstrap(None)          # the context is left on the corpus, not on the resample
+    else:
+        components = _nmf_topics_host(A, k, kwargs)
+    last_nmf_path = "device" if on_device else "host"
+    topics = np.array(components, dtype=np.float64, order="C")
     normalize(topics, axis=1)
     return topics
 
 
 def _ensemble_of_nmf_topics(X, k, n_runs, **kwargs):
-    """model="nmf" branch of ensemble_of_topics (enstop_.py:199-231), serial on the host."""
+    """model="nmf" branch of ensemble_of_topics (enstop_.py:199-231): the members one after the other, on the host or --
+    one upload for all of them -- on one device context."""
+    global last_nmf_path
+    from .utils import normalize
+    from . import nmf as _nmf
     kw = {key: kwargs[key] for key in ("bootstrap", "random_state", "init", "beta_loss", "alpha", "solver")
           if key in kwargs}
-    return np.vstack([nmf_topics(X, k, **kw) for _ in range(n_runs)])
+    backend, device = kwargs.get("nmf_backend", None), kwargs.get("device", None)
+    if not _nmf.use_device(backend, device, **_nmf_config(kw)):
+        return np.vstack([nmf_topics(X, k, backend="host", **kw) for _ in range(n_runs)])
+    A = (X.tocsr() if issparse(X) else csr_matrix(X)).astype(np.float32, copy=False)
+    eng = get_engine(device)
+    out = []
+    with eng.lock:
+        eng.upload_csr(A)
+        try:
+            for _ in range(n_runs):
+                topics = np.array(_nmf_topics_on_engine(eng, A, k, kw), dtype=np.float64, order="C")
+                normalize(topics, axis=1)
+                out.append(topics)
+        finally:
+            eng.bootstrap(None)
+    last_nmf_path = "device"
+    return np.vstack(out)
 
 
 def ensemble_of_topics(X, k, model="plsa", n_jobs=4, n_runs=16, parallelism="dask", **kwargs):
     """All topics of `n_runs` bootstrapped fits stacked to (n_runs * k, n_words), enstop_.py:164-231.
-    model="plsa": on the GPU(s), see `_ensemble_of_plsa_topics`; model="nmf": scikit-learn on the host."""
+    model="plsa": on the GPU(s), see `_ensemble_of_plsa_topics`; model="nmf": scikit-learn on the host, or the device with
+    nmf_backend="device" / ENSTOP_AMD_NMF (see `nmf_topics`)."""
     if model == "nmf":
         return _ensemble_of_nmf_topics(X, k, n_runs, **kwargs)
     if model != "plsa":
