@@ -1,19 +1,14 @@
 """In-tree build of libplsa_hip.so for gfx950:  python -m enstop_amd.build"""
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "plsa_hip.hip")
-DEPS = [SRC, os.path.join(HERE, "csrc", "plsa_kernels.hpp"), os.path.join(HERE, "csrc", "plsa_member_kernels.hpp"),
-        os.path.join(HERE, "csrc", "plsa_members.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_members.h"), os.path.join(HERE, "csrc", "plsa_ref_kernels.hpp"),
-        os.path.join(HERE, "csrc", "plsa_synth.hpp"), os.path.join(HERE, "csrc", "mt_jump.hpp"),
-        os.path.join(os.path.dirname(HERE), "include", "plsa_hip.h"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_diag.h"),
-        os.path.join(HERE, "csrc", "plsa_metric_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_metrics.h"),
-        os.path.join(os.path.dirname(HERE), "include", "plsa_hip_blocked.h"),
-        os.path.join(HERE, "csrc", "plsa_embed_kernels.hpp"), os.path.join(os.path.dirname(HERE), "include", "plsa_hip_embed.h"),
-        os.path.join(HERE, "csrc", "plsa_nmf_kernels.hpp"), os.path.join(HERE, "csrc", "plsa_nmf.hpp"),
-        os.path.join(os.path.dirname(HERE), "include", "plsa_hip_nmf.h")]
+# everything the one translation unit is made of: a new file is a dependency without being listed
+DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip")) + glob.glob(os.path.join(HERE, "csrc", "*.hpp"))
+              + glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h")))
 OUT = os.path.join(HERE, "libplsa_hip.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))

@@ -1928,38 +1928,6 @@ int run_ref_em_blocked(plsa_ctx *c, float thresh, const float *d_sw, bool update
     return 0;
 }
 
-// One materialised EM iteration of a driver (plsa_fit, plsa_refit): E-step into P(z|w,d), M-step from it -- in the reference
-// arithmetic under a budget (plsa_set_p_budget) block by block when the plan has more than one block.
-int run_driver_iteration(plsa_ctx *c, float thresh, const float *d_sw, bool update_v) {
-    bool blocked = false;
-    if (c->ref_sums && c->p_budget > 0) {
-        if (c->P.borrowed || c->p_lent)
-            return fail(c, "plsa_set_p_budget: a budget and a P(z|w,d) buffer that is %s do not mix -- end the loan or set the budget to 0",
-                        c->P.borrowed ? "borrowed (plsa_p_borrow)" : "lent out (plsa_p_reserve)");
-        CHK(ensure_ref_blocks(c));
-        blocked = c->ref_blocks.blocks() > 1;
-        if (c->P.cap > (size_t)c->p_budget) {      // left by a call without the budget: it goes before anything is allocated
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream2));
-            c->P.release();
-            c->p_state.invalidate();
-        }
-    }
-    if (blocked) CHK(run_ref_em_blocked(c, thresh, d_sw, update_v));
-    else {
-        CHK(run_e_step(c, thresh));
-        CHK(run_m_step_from_p(c, d_sw, update_v, nullptr));
-    }
-    if (c->ref_sums) {
-        plsa_ctx::PBlockInfo &pi = c->p_block_info;
-        pi.budget = c->p_budget;
-        pi.blocks = blocked ? c->ref_blocks.blocks() : 1;
-        pi.largest = blocked ? c->ref_blocks.largest : c->nnz;
-        pi.p_bytes = (int64_t)c->P.cap;
-    }
-    return 0;
-}
-
 // plsa.py:372-386 as ONE float32 running sum over the non-zeros (PLSA_REFERENCE_LL)
 int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out) {
     if (c->sharded) return fail(c, "the reference arithmetic has no doc-sharded form");
@@ -1989,26 +1957,6 @@ int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *out = c->h_ll[0];
     return 0;
-}
-
-// PLSA_REFERENCE_SUMS / PLSA_REFERENCE_LL of a driver call: in force for that call on top of plsa_set_arithmetic's setting
-struct ArithmeticScope {
-    plsa_ctx *c;
-    bool sums, ll;
-    ArithmeticScope(plsa_ctx *c_, int flags) : c(c_), sums(c_->ref_sums), ll(c_->ref_ll) {
-        if (flags & PLSA_REFERENCE_SUMS) c->ref_sums = true;
-        if (flags & PLSA_REFERENCE_LL) c->ref_ll = true;
-    }
-    ~ArithmeticScope() { c->ref_sums = sums; c->ref_ll = ll; }
-};
-
-// the reference's stop test, plsa.py:634-638: float32 arithmetic, float64 comparison with tolerance
-// (block_parallel_plsa.py:329-331 has no `change == 0` arm: zero_arm = false)
-bool stop_test(float cur, float &prev, double tol, bool zero_arm = true) {
-    const float change = fabsf(cur - prev);
-    if ((zero_arm && change == 0.0f) || (double)(change / fabsf(cur)) < tol) return true;
-    prev = cur;
-    return false;
 }
 
 // the PLSA_* knobs a context reads when it is created (a member context of a batch reads them like its leader)
@@ -2513,368 +2461,6 @@ int plsa_log_likelihood(plsa_ctx *c, const float *sw, double *ll) {
     const float *d_sw = nullptr;
     CHK(upload_sw(c, sw, &d_sw));
     return run_loglik(c, d_sw, ll);
-}
-
-// plsa_fit_inner, enstop/plsa.py:583-640.
-//
-// Materialised mode (flags without PLSA_FUSED) follows the reference's kernel sequence literally:
-// E-step -> M-step -> (every n_iter_per_test iterations) log-likelihood.
-//
-// Fused mode never writes P(z|w,d).  The log-likelihood the reference evaluates after iteration i
-// (i % n_iter_per_test == 0) is the likelihood of the factors that iteration i+1 reads, so it is
-// accumulated for free inside iteration i+1's document pass; the stop decision therefore arrives one
-// pass late and, when it says "stop", iteration i+1's output (sitting in the alternate buffers) is
-// discarded by not swapping -- the returned factors and iteration count are exactly the reference's.
-int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
-             float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_fit: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
-    ArithmeticScope arithmetic_scope(c, flags);
-    if ((c->ref_sums || c->ref_ll) && (flags & PLSA_SHARDED))
-        return fail(c, "plsa_fit: PLSA_REFERENCE_SUMS / PLSA_REFERENCE_LL have no doc-sharded form (the reference's sums are single chains over all non-zeros)");
-    // the reference arithmetic IS the reference's kernel sequence (E-step into P(z|w,d), M-step from it, likelihood): there is
-    // one such arithmetic, so PLSA_FUSED has nothing to select there and is ignored
-    const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll, trace = flags & PLSA_TRACE_LL;
-    const bool zero_arm = !(flags & PLSA_STOP_NO_ZERO_ARM);
-    c->fit_info.fused = fused;
-    struct ShardedScope {           // PLSA_SHARDED: this context's rows are one shard of the corpus
-        plsa_ctx *c;
-        ShardedScope(plsa_ctx *c_, bool on) : c(c_) { c->sharded = on; }
-        ~ShardedScope() { c->sharded = false; }
-    } sharded_scope(c, (flags & PLSA_SHARDED) != 0);
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    // plsa.py:606-628: with use_sample_weights == False the M-step ignores the weights, the
-    // log-likelihood (plsa.py:591, 631) still applies them
-    const float *d_sw_m = (flags & PLSA_SW_LL_ONLY) ? nullptr : d_sw;
-    int nll = 0, iters = 0;
-    double ll = 0.0;
-    float prev = 0.f;
-    // plsa.py:591: the likelihood of the initial factors.  The fused schedule gets it for free from the
-    // first iteration's document pass (which reads exactly those factors) instead of a separate launch.
-    bool first_ll_in_pass = fused && n_iter > 0;
-    if (!first_ll_in_pass) {
-        CHK(run_loglik(c, d_sw, &ll));
-        prev = (float)ll;
-        if (ll_trace) ll_trace[nll] = prev;
-        nll++;
-    }
-
-    if (!fused) {
-        struct ESw { plsa_ctx *c; ~ESw() { c->ref_e_sw = nullptr; } } e_sw_guard{c};
-        c->ref_e_sw = d_sw_m;               // (reference arithmetic: the E-step leaves its tile sums with the weights the M-step will use)
-        for (int i = 0; i < n_iter; ++i) {
-            CHK(run_driver_iteration(c, thresh, d_sw_m, true));      // plsa.py:597, 606-628
-            iters++;
-            if (i % n_iter_per_test == 0) {                          // plsa.py:630
-                if (i == n_iter - 1 && !trace) break;                // outcome cannot matter any more
-                CHK(run_loglik(c, d_sw, &ll));
-                const float cur = (float)ll;
-                if (ll_trace) ll_trace[nll] = cur;
-                nll++;
-                if (stop_test(cur, prev, tolerance, zero_arm)) break;
-            }
-        }
-    } else {
-        bool pending = false;  // a test is due on the factors currently in (cu, cv)
-        bool stopped = false;
-        const bool graph_requested = ((flags & PLSA_GRAPH) || c->graph) && !c->sharded && !c->timing;
-        // small corpora: column chain and document pass as two pipelines that exchange events (see below)
-        const bool pipelined = c->overlap && !c->sharded && !graph_requested && c->pipeline &&
-                               (double)c->nnz * c->kp < c->overlap_full_limit;
-        c->fit_info.pipelined = pipelined;
-        if (pipelined) {      // everything enqueued so far (factors, corpus) precedes both pipelines
-            HIPCHK(c, hipEventRecord(c->ev_row, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_row, 0));
-            HIPCHK(c, hipEventRecord(c->ev_tail, c->stream2));
-        }
-        struct PipelineJoin {    // whatever way the loop is left, the column chain has finished before the call returns
-            plsa_ctx *c; bool on;
-            ~PipelineJoin() { if (on) { (void)hipStreamSynchronize(c->stream2); } }
-        } pipeline_join{c, pipelined};
-        // Speculation across a likelihood test.  The test after iteration i - 1 rides on iteration i's document pass; the
-        // host used to wait for it before enqueuing iteration i + 1 -- an idle chip for one host round trip plus the launch
-        // latency of the next passes, every n_iter_per_test iterations (config 2: ~40 us per test = 2.3 % of the run).
-        // With a THIRD set of factor buffers iteration i + 1 is enqueued first (it reads iteration i's output and writes the
-        // third set, so the factors a "stop" must return are still untouched) and the host then waits for the likelihood
-        // alone.  "Stop" discards two iterations instead of one; the returned factors, count and trace are the same.
-        const bool speculate = (c->speculate > 0 || (c->speculate < 0 && (double)c->nnz * c->kp < c->overlap_full_limit)) &&
-                               !c->sharded && !graph_requested && n_iter_per_test >= 2 && n_iter >= 3;
-        struct Rot3Scope {       // leaves cu, cv in {0, 1} (everything outside this loop addresses the alternate as 1 - cu)
-            plsa_ctx *c;
-            ~Rot3Scope() {
-                if (!c->rot3) return;
-                c->rot3 = false;
-                if (c->cu == 2) { std::swap(c->U[2], c->U[0]); c->cu = 0; }
-                if (c->cv == 2) { std::swap(c->Vt[2], c->Vt[0]); c->cv = 0; }
-            }
-        } rot3_scope{c};
-        c->fit_info.speculated = speculate;
-        if (speculate) {
-            CHK(ensure(c, c->U[2], sizeof(float) * (size_t)c->n * c->kp));
-            CHK(ensure(c, c->Vt[2], sizeof(float) * (size_t)c->m * c->kp));
-            c->rot3 = true;
-        }
-        bool first_wait = false;     // the initial likelihood is in flight (speculating loop)
-        int first_slot = 0;
-        auto collect_first = [&]() -> int {
-            if (!first_wait) return 0;
-            first_wait = false;
-            CHK(wait_ll(c, &ll));
-            prev = (float)ll;
-            if (ll_trace) ll_trace[first_slot] = prev;
-            return 0;
-        };
-        auto advance = [&]() {
-            if (c->rot3) { c->cu = (c->cu + 1) % 3; c->cv = (c->cv + 1) % 3; } else { c->cu ^= 1; c->cv ^= 1; }
-        };
-        // one fused EM iteration from the factors in (cu, cv) into the alternate buffers (no swap here)
-        auto enqueue_iteration = [&](bool want_ll, int *blocks) -> int {
-            // PLSA_SHARDED: every collective of the communicator goes on c->stream in program order (accumulator
-            // all-reduce, then the likelihood all-reduce) -- no second stream, identical order on every rank
-            const bool overlap = c->overlap && !c->sharded;
-            if (overlap && (double)c->nnz * c->kp < c->overlap_full_limit) {
-                // small problems leave CUs idle inside each kernel (measured: config 1 0.50 -> 0.37 ms,
-                // config 2 0.43 -> 0.37 ms per iteration; neutral at config 3, -6 % at config 5):
-                // the document pass (VALU-heavy, gathers the small topic table) and the column chain
-                // (fabric-bound gathers of P(z|d) rows) read the same current factors and write
-                // disjoint outputs: run them on two streams so their stalls overlap
-                CHK(ensure_packed_csc(c));
-                CHK(ensure_packed_csr(c));
-                CHK(ensure_ritems(c));
-                const int *unused = nullptr;
-                if (!c->ritems.use) CHK(ensure_roworder(c, &unused));
-                if (pipelined) {
-                    // The column chain of successive iterations is one dependency chain (column pass -> tail -> next
-                    // column pass): it stays back to back on the second stream, and the two streams only exchange
-                    // "document pass i done" / "column chain i done" events.  A fork + join through the first stream
-                    // put two cross-stream hops (17 us of 121 at config 1) between tail i and column pass i+1.
-                    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail, 0));      // P(w|z) of the previous chain
-                    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_row, 0));      // P(z|d) of the previous document pass
-                    {
-                        LaunchOn on2(c, c->stream2);
-                        CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
-                        CHK(run_col_tail(c));
-                    }
-                    HIPCHK(c, hipEventRecord(c->ev_tail, c->stream2));
-                    CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
-                    HIPCHK(c, hipEventRecord(c->ev_row, c->stream));
-                    return 0;
-                }
-                HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-                {
-                    LaunchOn on2(c, c->stream2);
-                    CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
-                    CHK(run_col_tail(c));
-                }
-                HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-                CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            } else if (overlap) {
-                // large problems: both passes saturate the memory system on their own (running them
-                // side by side is neutral at config 3, -6 % at config 5), but the short chain of
-                // column sums / normalisation after the column pass leaves the chip nearly idle --
-                // it runs on the second stream underneath the document pass
-                CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
-                HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-                HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-                {
-                    LaunchOn on2(c, c->stream2);
-                    CHK(run_col_tail(c));
-                }
-                HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-                CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            } else {
-                CHK(run_row_pass(c, false, want_ll, d_sw, thresh, nullptr, blocks));
-                CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
-                CHK(run_col_tail(c));
-            }
-            return 0;
-        };
-        // PLSA_GRAPH (flag or environment): the iterations between two likelihood tests replayed from a hipGraph
-        // of TWO iterations (the double buffers alternate, a pair returns to the starting buffers; the single
-        // eager iteration of a likelihood test flips the parity, hence one graph per starting pair), captured
-        // from the launch sequence above.  Kernel arguments are baked into the graph, so it lives for this
-        // call only.  Off by default: measured neutral (the host is not the bound, and a dependent kernel
-        // boundary costs the same 1.5 us eager or replayed)
-        const bool use_graph = graph_requested;
-        hipGraphExec_t gexecs[4] = {nullptr, nullptr, nullptr, nullptr};   // one per starting buffer pair (cu, cv)
-        struct GraphGuard {
-            hipGraphExec_t (&g)[4];
-            ~GraphGuard() { for (auto e : g) if (e) (void)hipGraphExecDestroy(e); }
-        } graph_guard{gexecs};
-        for (int i = 0; i < n_iter; ++i) {
-            int blocks = 0;
-            const bool want_ll = pending || first_ll_in_pass;
-            if (use_graph && !want_ll && i + 1 < n_iter && (i % n_iter_per_test) != 0) {
-                // iterations i and i + 1, neither carries a likelihood test
-                hipGraphExec_t &gexec = gexecs[c->cu * 2 + c->cv];
-                if (!gexec) {
-                    hipGraph_t graph = nullptr;
-                    HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                    int rc = enqueue_iteration(false, &blocks);
-                    c->cu ^= 1; c->cv ^= 1;
-                    if (!rc) rc = enqueue_iteration(false, &blocks);
-                    c->cu ^= 1; c->cv ^= 1;
-                    const hipError_t e_end = hipStreamEndCapture(c->stream, &graph);
-                    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                    HIPCHK(c, e_end);
-                    const hipError_t e_inst = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-                    (void)hipGraphDestroy(graph);
-                    HIPCHK(c, e_inst);
-                }
-                HIPCHK(c, hipGraphLaunch(gexec, c->stream));
-                c->fit_info.graph_launches++;
-                iters += 2;
-                ++i;
-                pending = (i % n_iter_per_test == 0);
-                continue;
-            }
-            CHK(enqueue_iteration(want_ll, &blocks));
-            if (first_ll_in_pass) {
-                if (speculate) {       // nothing is decided on the initial likelihood: it is collected when the first test needs it
-                    CHK(finish_ll(c, blocks, nullptr));
-                    first_wait = true;
-                    first_slot = nll;
-                } else {
-                    CHK(finish_ll(c, blocks, &ll));
-                    prev = (float)ll;
-                    if (ll_trace) ll_trace[nll] = prev;
-                }
-                nll++;
-                first_ll_in_pass = false;
-            } else if (pending && speculate && i + 1 < n_iter) {
-                CHK(collect_first());
-                CHK(finish_ll(c, blocks, nullptr));            // on its way to the host; not waited for yet
-                const int su = c->cu, sv = c->cv;              // the factors a stop returns
-                advance();                                     // iteration i + 1 reads iteration i's output ...
-                int blocks2 = 0;
-                const int rc = enqueue_iteration(false, &blocks2);   // ... and writes the third set (n_iter_per_test >= 2: no test rides on it)
-                if (rc) { c->cu = su; c->cv = sv; return rc; }
-                CHK(wait_ll(c, &ll));
-                const float cur = (float)ll;
-                if (ll_trace) ll_trace[nll] = cur;
-                nll++;
-                if (stop_test(cur, prev, tolerance, zero_arm)) {     // discard both passes
-                    c->cu = su; c->cv = sv;
-                    stopped = true;
-                    break;
-                }
-                advance();
-                iters += 2;
-                ++i;                                           // (iteration i + 1 is done; it is no multiple-of-test successor)
-                pending = (i % n_iter_per_test == 0);
-                continue;
-            } else if (pending) {
-                CHK(collect_first());
-                CHK(finish_ll(c, blocks, &ll));
-                const float cur = (float)ll;
-                if (ll_trace) ll_trace[nll] = cur;
-                nll++;
-                if (stop_test(cur, prev, tolerance, zero_arm)) { stopped = true; break; }  // discard this pass
-            }
-            advance();
-            iters++;
-            pending = (i % n_iter_per_test == 0);
-        }
-        CHK(collect_first());
-        if (pipelined) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail, 0));   // the last column chain precedes whatever follows
-        if (!stopped && pending && trace) {  // test of the last iteration: result-neutral
-            CHK(run_loglik(c, d_sw, &ll));
-            if (ll_trace) ll_trace[nll] = (float)ll;
-            nll++;
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = nll;
-    return 0;
-}
-
-// plsa_refit_inner, enstop/plsa.py:884-920: topics frozen, only P(z|d) moves.
-int plsa_refit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
-               float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_refit: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
-    ArithmeticScope arithmetic_scope(c, flags);
-    const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll, trace = flags & PLSA_TRACE_LL;
-    c->fit_info.fused = fused;
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    int nll = 0, iters = 0;
-    double ll = 0.0;
-    float prev = 0.f;
-    bool first_ll_in_pass = fused && n_iter > 0;       // as in plsa_fit: the initial likelihood rides on pass 0
-    if (!first_ll_in_pass) {
-        CHK(run_loglik(c, d_sw, &ll));
-        prev = (float)ll;
-        if (ll_trace) ll_trace[nll] = prev;
-        nll++;
-    }
-    // plsa.py:913-918: the test only acts on a positive log-likelihood
-    auto refit_stop = [&](float cur) {
-        if (cur > 0.0f) {
-            const float change = fabsf(cur - prev);
-            if ((double)(change / fabsf(cur)) < tolerance) return true;
-            prev = cur;
-        }
-        return false;
-    };
-    if (!fused) {
-        struct NoSums { plsa_ctx *c; ~NoSums() { c->ref_e_no_sums = false; } } no_sums_guard{c};
-        c->ref_e_no_sums = true;            // (reference arithmetic: no norm_pwz chain follows these E-steps, their tile sums would be wasted)
-        for (int i = 0; i < n_iter; ++i) {
-            CHK(run_driver_iteration(c, thresh, nullptr, false));
-            iters++;
-            if (i % n_iter_per_test == 0) {
-                if (i == n_iter - 1 && !trace) break;
-                CHK(run_loglik(c, d_sw, &ll));
-                const float cur = (float)ll;
-                if (ll_trace) ll_trace[nll] = cur;
-                nll++;
-                if (refit_stop(cur)) break;
-            }
-        }
-    } else {
-        bool pending = false, stopped = false;
-        for (int i = 0; i < n_iter; ++i) {
-            int blocks = 0;
-            // the refit M-step ignores sample weights for P(z|d) (plsa.py:806-809); they only enter
-            // the log-likelihood, which this pass accumulates when a test is pending
-            CHK(run_row_pass(c, false, pending || first_ll_in_pass, d_sw, thresh, nullptr, &blocks));
-            if (first_ll_in_pass) {
-                CHK(finish_ll(c, blocks, &ll));
-                prev = (float)ll;
-                if (ll_trace) ll_trace[nll] = prev;
-                nll++;
-                first_ll_in_pass = false;
-            } else if (pending) {
-                CHK(finish_ll(c, blocks, &ll));
-                const float cur = (float)ll;
-                if (ll_trace) ll_trace[nll] = cur;
-                nll++;
-                if (refit_stop(cur)) { stopped = true; break; }
-            }
-            c->cu ^= 1;
-            iters++;
-            pending = (i % n_iter_per_test == 0);
-        }
-        if (!stopped && pending && trace) {
-            CHK(run_loglik(c, d_sw, &ll));
-            if (ll_trace) ll_trace[nll] = (float)ll;
-            nll++;
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = nll;
-    return 0;
 }
 
 // ---- doc-sharded single fit: local accumulate / (caller all-reduces) / finish -----------------------
@@ -3782,5 +3368,6 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 
 }  // extern "C"
 
+#include "plsa_drivers.hpp"   // plsa_fit, plsa_refit: backends of the likelihood-test loop (plsa_fit_schedule.hpp)
 #include "plsa_members.hpp"   // batched ensemble members (include/plsa_hip_members.h)
 #include "plsa_nmf.hpp"       // KL-divergence NMF (include/plsa_hip_nmf.h)

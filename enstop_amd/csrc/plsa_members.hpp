@@ -153,7 +153,7 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
               int32_t *n_ll) {
     plsa_ctx *L = b->leader, *c0 = b->ctx[who[0]].get();
     const int G = (int)who.size();
-    const bool trace = flags & PLSA_TRACE_LL, zero_arm = !(flags & PLSA_STOP_NO_ZERO_ARM);
+    const bool trace = flags & PLSA_TRACE_LL;
     HIPCHK(L, hipMemcpyAsync(b->table.p, rows.data(), sizeof(plsa::MemberArgs) * (size_t)G, hipMemcpyHostToDevice, L->stream));
     HIPCHK(L, hipStreamSynchronize(L->stream));      // (`rows` is the caller's; and the members' builders have finished)
     const plsa::MemberArgs *table = b->table.as<plsa::MemberArgs>();
@@ -219,12 +219,11 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
         }));
         return launch_check(L, "k_col_pass_members");
     };
-    std::vector<float> prev(G, 0.f);
-    std::vector<int> nll(G, 0), iters(G, 0);
-    auto record = [&](int g, float v) {
-        if (ll_trace && nll[g] < ll_cap) ll_trace[(size_t)who[g] * ll_cap + nll[g]] = v;
-        nll[g]++;
-    };
+    std::vector<plsa::fit::Tests> tests;
+    for (int g = 0; g < G; ++g)
+        tests.push_back({ll_trace ? ll_trace + (size_t)who[g] * ll_cap : nullptr, tolerance,
+                         (flags & PLSA_STOP_NO_ZERO_ARM) ? plsa::fit::FIT_NO_ZERO_ARM : plsa::fit::FIT, n_iter_per_test, ll_cap});
+    std::vector<int> iters(G, 0);
     bool pending = false, first = true;
     for (int i = 0; i < n_iter && live; ++i) {
         const bool want_ll = pending || first;
@@ -240,17 +239,15 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
             HIPCHK(L, hipStreamSynchronize(L->stream));
             for (int g = 0; g < G; ++g) {
                 if (!((live >> g) & 1ull)) continue;
-                const float cur = (float)b->h_ll[g];
                 b->last_ll[who[g]] = b->h_ll[g];
-                if (first) { prev[g] = cur; record(g, cur); continue; }
-                record(g, cur);
-                if (stop_test(cur, prev[g], tolerance, zero_arm)) live &= ~(1ull << g);    // this pass is discarded: no swap
+                if (first) tests[g].initial(b->h_ll[g]);
+                else if (tests[g].test(b->h_ll[g])) live &= ~(1ull << g);    // this pass is discarded: no swap
             }
             first = false;
         }
         cu ^= live; cv ^= live;
         for (int g = 0; g < G; ++g) if ((live >> g) & 1ull) iters[g]++;
-        pending = (i % n_iter_per_test == 0);
+        pending = tests[0].due_after(i);
     }
     HIPCHK(L, hipStreamSynchronize(L->stream));
     for (int g = 0; g < G; ++g) {
@@ -262,10 +259,10 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
             double ll = 0.0;
             CHK(member_rc(L, c, run_loglik(c, nullptr, &ll)));
             b->last_ll[who[g]] = ll;
-            record(g, (float)ll);
+            tests[g].trailing(ll);
         }
         iters_done[who[g]] = iters[g];
-        n_ll[who[g]] = nll[g];
+        n_ll[who[g]] = tests[g].count;
     }
     return 0;
 }
