@@ -189,12 +189,11 @@ struct FusedFitBackend : RidingLikelihood {
         }
         const bool pipelines = topology == Topology::PIPELINES, tail_only = topology == Topology::FORK_TAIL;
         if (tail_only) CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
-        else {
-            CHK(ensure_packed_csc(c));
-            CHK(ensure_packed_csr(c));
-            CHK(ensure_ritems(c));
-            const int *unused = nullptr;
-            if (!c->ritems.use) CHK(ensure_roworder(c, &unused));
+        else {                       // both passes' structures and scratch are built on c->stream before anything forks
+            ColLaunch col;
+            RowLaunch row;
+            CHK(prepare_col_pass(c, false, col));
+            CHK(prepare_row_pass(c, false, want_ll, row));
         }
         if (pipelines) {
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail, 0));      // P(w|z) of the previous chain

@@ -39,6 +39,7 @@
 #include "mt_jump.hpp"
 #include "plsa_embed_kernels.hpp"
 #include "plsa_kernels.hpp"
+#include "plsa_launch_plan.hpp"
 #include "plsa_member_kernels.hpp"
 #include "plsa_metric_kernels.hpp"
 #include "plsa_nmf_kernels.hpp"
@@ -595,10 +596,8 @@ int dispatch_shape(plsa_ctx *c, Fn &&fn) {
     return fail(c, "unsupported topic count k=%d (max 1024)", c->k);
 }
 
-// The two fused passes gather rows of a factor table by index with 32-bit byte offsets (plsa_kernels.hpp: gather_row).
-// A table of 4 GB or more (rows * kp * 4 >= 2^32: e.g. 20 M documents at k = 64) takes the WIDE instantiations instead:
-// 64-bit row addresses, run-time kp -- same arithmetic, same results.  PLSA_FORCE_WIDE=1 selects them for any size (tests).
-bool table_is_wide(plsa_ctx *c, i64 rows) { return c->force_wide || (double)rows * c->kp * 4.0 >= 4294967296.0; }
+// a gathered table of 4 GB or more takes the WIDE instantiations (plsa_launch_plan.hpp); PLSA_FORCE_WIDE=1: any size
+bool table_is_wide(plsa_ctx *c, i64 rows) { return plsa::plan::table_is_wide(rows, c->kp, c->force_wide); }
 
 template <class Fn>
 int dispatch_shape_gather(plsa_ctx *c, bool wide, Fn &&fn) {
@@ -634,9 +633,7 @@ inline int out_u(const plsa_ctx *c) { return c->rot3 ? (c->cu + 1) % 3 : 1 - c->
 inline int out_v(const plsa_ctx *c) { return c->rot3 ? (c->cv + 1) % 3 : 1 - c->cv; }
 
 int grid_for(plsa_ctx *c, i64 work_items, int items_per_block) {
-    i64 need = (work_items + items_per_block - 1) / items_per_block;
-    if (need < 1) need = 1;
-    return (int)std::min<i64>(need, c->grid_cap);
+    return plsa::plan::grid_for(work_items, items_per_block, c->grid_cap);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -704,27 +701,14 @@ int ensure_roworder(plsa_ctx *c, const int **out) {
 
 int exclusive_sum_int(plsa_ctx *c, const int *in, int *out, i64 count);
 
-// Decide whether the document pass should run over row items, and build them.  Row ownership needs
-// enough rows to fill 256 CUs x 32 waves x (64/LPN) groups, and rows of comparable length.
+// Decide whether the document pass should run over row items (plsa_launch_plan.hpp: row_items), and build them.
 int ensure_ritems(plsa_ctx *c) {
     if (c->ritems.valid) return 0;
     const i64 n = c->n;
-    const i64 group_slots = (i64)c->prop.multiProcessorCount * 32 * (64 / std::max(1, c->row_lpn));
-    const double avg = (double)c->nnz / (double)std::max<i64>(n, 1);
-    // the decision is made for 64-entry items (documents averaging more than 128 entries: config 2's 100-entry documents
-    // stay whole -- items cost it 15 % in the two-stream schedule); the item LENGTH then follows the size of the corpus:
-    // about one item per group slot, a power of two in [16, 64] (20NG shape: 45 entries per slot -> 32; with the final
-    // kernels of round 4 row items of 16 / 24 / 32 / 40 / 48 / 64 entries give 9.9 / 10.7 / 11.1 / 11.1 / 10.9 / 10.4 k
-    // iterations/s at config 1, profiles/r04_small_corpus_item_lengths.txt)
-    const int rseg_decide = c->rseg_override ? c->rseg_override : 64;
-    c->ritems.use = c->ritems_mode == 1 || (c->ritems_mode < 0 && n < 2 * group_slots && avg > 2.0 * rseg_decide);
-    if (c->rseg_override) c->ritems.seg = c->rseg_override;
-    else {
-        const i64 per_slot = c->nnz / std::max<i64>(group_slots, 1);
-        int r = 16;
-        while (r * 2 <= per_slot && r < 64) r *= 2;
-        c->ritems.seg = r;
-    }
+    const plsa::plan::RowItems ri = plsa::plan::row_items(n, c->nnz, c->prop.multiProcessorCount, c->row_lpn, c->ritems_mode,
+                                                          c->rseg_override);
+    c->ritems.use = ri.use;
+    c->ritems.seg = ri.seg;
     c->ritems.n = 0;
     if (c->ritems.use) {
         CHK(ensure(c, c->ritems.first, sizeof(int) * (size_t)(n + 1)));
@@ -787,25 +771,7 @@ int exclusive_sum_int(plsa_ctx *c, const int *in, int *out, i64 count) {
 int ensure_csc(plsa_ctx *c) {
     if (c->csc.valid) return 0;
     CHK(ensure_rowidx(c));
-    {   // item length: a group walks seg/LPN dependent gather batches per item, so small problems want
-        // short items (enough items to fill the chip: config 1 0.244 -> 0.094 ms at 16) and large
-        // ones long items (fewer partial rows: 256 measured best at config 3)
-        const i64 slots = (i64)c->prop.multiProcessorCount * 32 * (64 / std::max(1, c->lpn));
-        // (round 4, final kernels: about 1.25 group slots per item instead of 4 -- config 1 now cuts its columns into
-        //  32-entry items, 16 / 32 / 48 / 64 -> 10.5 / 11.1 / 11.0 / 10.9 k iterations/s with 32-entry row items; config 2
-        //  64 instead of 32: the same within noise)
-        i64 want = c->nnz / std::max<i64>(slots + slots / 4, 1);
-        int seg = 16;
-        // large corpora: with the XCD stretches balanced, SHORTER items win (an item then spans fewer documents
-        // and stays inside the band its XCD's L2 holds): config 3 (k = 64) 256 / 128 / 96 / 64 / 48 entries ->
-        // 268 / 269 / 271 / 274 / 272 iterations/s before the band-major order, flat from 48 to 128 with it; config 5
-        // (k = 128) 256 / 128 / 64 -> 25.3 / 27.6 / 28.6.
-        // Items of one length for every column: a chunk's groups (and a wave's) wait for their longest item --
-        // long items for the Zipf-head words only (256 entries, the others 64) cost 1.96 -> 3.0 ms at config 3
-        const int cap = 64;
-        while (seg * 2 <= want && seg < cap) seg *= 2;
-        c->csc.seg = c->seg_override ? c->seg_override : seg;
-    }
+    c->csc.seg = plsa::plan::col_item_len(c->nnz, c->prop.multiProcessorCount, c->lpn, c->seg_override);
     const i64 nnz = c->nnz, m = c->m;
     CHK(ensure(c, c->csc.colptr, sizeof(int) * (size_t)(m + 1)));
     CHK(ensure(c, c->csc.row, sizeof(int) * (size_t)nnz));
@@ -865,13 +831,7 @@ int ensure_csc(plsa_ctx *c) {
     CHK(ensure(c, c->tmp2, sizeof(unsigned long long) * ni * 2));   // sort keys, sorted keys
     CHK(ensure(c, c->tmp1, sizeof(int) * ni));           // item ids
     unsigned long long *d_key = c->tmp2.as<unsigned long long>();
-    // band of the visiting order (PLSA_ORDER_BAND documents): 2 MB of P(z|d) rows from k = 64 on -- half an XCD's L2; 8192
-    // documents at config 3, 4096 at config 5.  Measured with the final kernels of round 4, config 3: 2048 / 6144 / 8192 /
-    // 10240 / 16384 / 32768 documents -> 313 / 318 / 319 / 316 / 303 / 254 iterations/s; config 5: 1024 / 3072 / 4096 / 6144 ->
-    // 29.0 / 29.4 / 29.9 / 29.8 (round 3 chose 512 KB with 256-entry items).  Narrow k-vectors stay at 512 KB (config 2:
-    // 8192 documents = 1 MB neutral, 16384 = 2 MB 2 % slower)
-    const int band_bytes = (c->kp >= 64 ? 2048 : 512) << 10;
-    const int band = c->order_band >= 0 ? c->order_band : std::max(64, band_bytes / (c->kp > 0 ? c->kp * 4 : 256));
+    const int band = plsa::plan::order_band(c->kp, c->order_band);   // band of the visiting order (PLSA_ORDER_BAND documents)
     // key = band index << len_bits | inverted column length (a column holds at most n entries); first document when band <= 0
     int len_bits = 1;
     while (((i64)1 << len_bits) <= c->n) ++len_bits;
@@ -979,22 +939,11 @@ int upload_sw(plsa_ctx *c, const float *sw, const float **d_sw) {
 
 // lane decomposition of a k-vector (see plsa_kernels.hpp) + invalidation of the structures that depend on it
 void set_shape(plsa_ctx *c, int k) {
-    const int kp = (k + 3) / 4 * 4;
-    c->k = k; c->kp = kp;
-    const int prev_lpn = c->struct_lpn, prev_row_lpn = c->struct_row_lpn;
-    int lpn = 1;
-    while (lpn < kp / 4 && lpn < 64) lpn *= 2;
-    // k >= 128: 8 floats per lane (two float4 chunks) -- fewer reduction/shuffle instructions per
-    // cell, each access still covers whole 128-B lines (measured: config 5 document pass -15 %)
-    if (lpn >= 32 && lpn * 4 >= kp && c->chunks_per_lane == 2) lpn /= 2;
-    c->lpn = lpn;
-    c->ch = (kp / 4 + lpn - 1) / lpn;
-    if (c->ch == 3) c->ch = 4;
-    // k = 64: the document pass runs as 8 lanes x 2 chunks (a wave covers 8 documents, one DPP step less per group sum,
-    // half the log-likelihood reductions per entry): its LL variant 1.94 -> 1.59 ms, the plain one 1.547 -> 1.530 ms at
-    // config 3, while the column pass is 3.5 % SLOWER in that shape (32 items per chunk) and keeps 16 x 1
-    c->row_lpn = c->lpn; c->row_ch = c->ch;
-    if (c->row_shape_8x2 && c->lpn == 16 && c->ch == 1 && kp == 64) { c->row_lpn = 8; c->row_ch = 2; }
+    const plsa::plan::LaneShape sh = plsa::plan::lane_shape(k, c->chunks_per_lane, c->row_shape_8x2);
+    const int prev_lpn = c->struct_lpn, prev_row_lpn = c->struct_row_lpn, lpn = sh.lpn;
+    c->k = k; c->kp = sh.kp;
+    c->lpn = sh.lpn; c->ch = sh.ch;
+    c->row_lpn = sh.row_lpn; c->row_ch = sh.row_ch;
     // the row-item decision and length follow the DOCUMENT pass' lane count (ensure_ritems), which changes between
     // kp = 60 and kp = 64 while lpn stays 16: watched on its own
     if (c->row_lpn != prev_row_lpn) {
@@ -1118,88 +1067,107 @@ int run_e_step(plsa_ctx *c, float thresh) {
     return 0;
 }
 
+// Compile-time choices of a pass' instantiation.  A bool picks its tag at run time; a caller that fixes a choice passes the
+// tag itself (std::false_type{}) and only that branch is instantiated.
+template <class Fn> void with_flag(bool v, Fn &&fn) { if (v) fn(std::true_type{}); else fn(std::false_type{}); }
+template <bool V, class Fn> void with_flag(std::integral_constant<bool, V> v, Fn &&fn) { fn(v); }
+
+// Instantiation of the document pass in lane shape Sh: fn(stream shape, FROM_P, LL, TINY).  Fused: the packed entry stream
+// when it is eligible; TINY: the denormal-norm rescue, compiled in for thresholds below TINY_THRESH only.  From P(z|w,d):
+// the two arrays, no likelihood, no rescue.
+template <class Sh, class FromP, class Fn>
+void select_row_pass(bool packed, FromP from_p, bool want_ll, bool tiny, Fn &&fn) {
+    with_flag(from_p, [&](auto FP) {
+        if constexpr (decltype(FP)::value) fn(Sh{}, FP, std::false_type{}, std::false_type{});
+        else with_flag(want_ll, [&](auto LL) {
+            with_flag(tiny, [&](auto TN) { if (packed) fn(plsa::Packed<Sh>{}, FP, LL, TN); else fn(Sh{}, FP, LL, TN); });
+        });
+    });
+}
+
+// Instantiation of the column pass in lane shape Sh: fn(stream shape, FROM_P, TIMED, TINY), as above
+template <class Sh, class FromP, class Timed, class Fn>
+void select_col_pass(bool packed, FromP from_p, Timed timed, bool tiny, Fn &&fn) {
+    with_flag(from_p, [&](auto FP) {
+        with_flag(timed, [&](auto TM) {
+            if constexpr (decltype(FP)::value) fn(Sh{}, FP, TM, std::false_type{});
+            else with_flag(tiny, [&](auto TN) { if (packed) fn(plsa::Packed<Sh>{}, FP, TM, TN); else fn(Sh{}, FP, TM, TN); });
+        });
+    });
+}
+
+// What one document pass is launched with: THE place its structures, scratch and grids are decided (plsa_launch_plan.hpp holds
+// the arithmetic).  Nothing here is cached: prepare_row_pass computes it from the context on every call; in the steady state
+// every builder and every `ensure` is a no-op.  The builders run on c->stream: called before a fork, it leaves nothing for
+// the second stream to build.
+struct RowLaunch {
+    plsa::plan::RowPass plan;
+    bool items, packed, xcd_rows;    // over row items / the packed entry stream / PLSA_ROW_XCD's schedule
+    const int *indptr, *colidx;      // colidx: the packed CSR stream when `packed`
+    const float *vals;
+    const int *order;                // visiting order of whole documents (nullptr over items, or unsorted)
+    const int *ritem_row, *ritem_start, *ritem_first;   // nullptr on whole documents
+    float *rpartial;                 // one k-vector per row item (nullptr on whole documents)
+    double *ll_partials;             // plan.grid partial sums (sized only when the pass carries the likelihood)
+    i64 n_ritems;
+    int rseg;
+};
+
+int prepare_row_pass(plsa_ctx *c, bool from_p, bool want_ll, RowLaunch &r) {
+    CHK(ensure_ritems(c));
+    r.items = c->ritems.use && c->ritems.n > 0;
+    // PLSA_ROW_XCD (experiment): the visiting list is ordered range by range (range = the documents of one eighth), longest
+    // document first inside a range
+    r.xcd_rows = !r.items && !from_p && c->sort_rows && row_xcd_range(c) > 0;
+    r.plan = plsa::plan::row_pass(c->n, c->ritems.n, r.items, c->row_lpn, c->grid_cap, r.xcd_rows);
+    r.order = nullptr;
+    if (!r.items) CHK(ensure_roworder(c, &r.order));
+    if (r.items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->ritems.n * c->kp));
+    if (want_ll) CHK(ensure(c, c->ll_partials, sizeof(double) * (size_t)r.plan.grid));
+    if (!from_p) CHK(ensure_packed_csr(c));
+    r.packed = !from_p && c->packed && c->pk_csr.ok;
+    r.indptr = c->indptr; r.colidx = r.packed ? c->pk_csr.buf.as<int>() : c->col; r.vals = c->val;
+    r.ritem_row = r.items ? c->ritems.row.as<int>() : nullptr;
+    r.ritem_start = r.items ? c->ritems.start.as<int>() : nullptr;
+    r.ritem_first = r.items ? c->ritems.first.as<int>() : nullptr;
+    r.rpartial = r.items ? c->rpartial.as<float>() : nullptr;
+    r.ll_partials = c->ll_partials.as<double>();
+    r.n_ritems = c->ritems.n; r.rseg = c->ritems.seg;
+    return 0;
+}
+
 // document-owned pass: writes U[1-cu]; optional LL partials of the current factors
 int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, float thresh,
                  float *d_norm_pdz, int *ll_blocks) {
-    CHK(ensure_ritems(c));
-    const bool items = c->ritems.use && c->ritems.n > 0;
-    int grid = grid_for(c, items ? c->ritems.n : c->n, 256 / c->row_lpn);
-    const int *order = nullptr;
-    // PLSA_ROW_XCD (experiment): one trip, grid a multiple of 8, XCD x takes the x-th eighth of the visiting list, which is
-    // ordered range by range (range = the documents of one eighth), longest document first inside a range
-    const int gpb_row = 256 / c->row_lpn;
-    const bool xcd_rows = !items && !from_p && c->sort_rows && row_xcd_range(c) > 0;
-    if (xcd_rows) grid = (int)(((c->n + gpb_row - 1) / gpb_row + 7) / 8 * 8);
-    if (!items) CHK(ensure_roworder(c, &order));
-    if (items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->ritems.n * c->kp));
-    const int *ri_row = items ? c->ritems.row.as<int>() : nullptr;
-    const int *ri_start = items ? c->ritems.start.as<int>() : nullptr;
-    float *rpart = items ? c->rpartial.as<float>() : nullptr;
-    const int rseg = c->ritems.seg;
-    const i64 n_ritems = c->ritems.n;
-    if (want_ll) CHK(ensure(c, c->ll_partials, sizeof(double) * (size_t)grid));
-    if (!from_p) CHK(ensure_packed_csr(c));
-    const bool packed = !from_p && c->packed && c->pk_csr.ok;
+    RowLaunch r;
+    CHK(prepare_row_pass(c, from_p, want_ll, r));
     CHK(dispatch_shape_row(c, [&](auto S) {
         using Sh = decltype(S);
-        const int *ip = c->indptr, *cl = packed ? c->pk_csr.buf.as<int>() : c->col;
-        const float *vl = c->val, *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
-        const float *P = p_base(c);
+        const float *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
         float *Un = c->U[out_u(c)].as<float>();
-        double *llp = c->ll_partials.as<double>();
         const int n = (int)c->n, kp = c->kp;
-        auto launch = [&](auto SS, auto FP, auto LL, auto TN, const char *name) {
-            Scope s(c, name);
+        select_row_pass<Sh>(r.packed, from_p, want_ll, thresh < plsa::TINY_THRESH, [&](auto SS, auto FP, auto LL, auto TN) {
+            Scope s(c, from_p ? "k_row_pass<P>" : want_ll ? "k_row_pass<fused,LL>" : "k_row_pass<fused>");
             hipLaunchKernelGGL((plsa::k_row_pass<decltype(SS), decltype(FP)::value, decltype(LL)::value, decltype(TN)::value>),
-                               dim3(grid), dim3(256), 0, c->ls, ip, cl, vl, n, order, U, Vt, P, Un,
-                               d_sw, d_norm_pdz, kp, thresh, llp, ri_row, ri_start, rseg, n_ritems, rpart, xcd_rows ? 1 : 0);
-        };
-        auto go = [&](auto FP, auto LL, auto TN, const char *name) {   // fused: the packed entry stream when it is eligible
-            if constexpr (!decltype(FP)::value) {
-                if (packed) { launch(plsa::Packed<Sh>{}, FP, LL, TN, name); return; }
-            }
-            launch(Sh{}, FP, LL, TN, name);
-        };
-        using T = std::true_type;
-        using F = std::false_type;
-        const bool tiny = thresh < plsa::TINY_THRESH;   // denormal-norm rescue: compiled in for these thresholds only
-        if (from_p) go(T{}, F{}, F{}, "k_row_pass<P>");
-        else if (want_ll) { if (tiny) go(F{}, T{}, T{}, "k_row_pass<fused,LL>"); else go(F{}, T{}, F{}, "k_row_pass<fused,LL>"); }
-        else { if (tiny) go(F{}, F{}, T{}, "k_row_pass<fused>"); else go(F{}, F{}, F{}, "k_row_pass<fused>"); }
-        if (items) {
+                               dim3(r.plan.grid), dim3(256), 0, c->ls, r.indptr, r.colidx, r.vals, n, r.order, U, Vt, p_base(c), Un,
+                               d_sw, d_norm_pdz, kp, thresh, r.ll_partials, r.ritem_row, r.ritem_start, r.rseg, r.n_ritems,
+                               r.rpartial, r.xcd_rows ? 1 : 0);
+        });
+        if (r.items) {
             Scope s(c, "k_row_reduce");
-            hipLaunchKernelGGL((plsa::k_row_reduce<Sh>), dim3(grid_for(c, c->n, 256 / Sh::LPN)), dim3(256), 0, c->ls,
-                               c->ritems.first.as<int>(), n, rpart, Un, d_norm_pdz, kp);
+            hipLaunchKernelGGL((plsa::k_row_reduce<Sh>), dim3(r.plan.reduce_grid), dim3(256), 0, c->ls,
+                               r.ritem_first, n, r.rpartial, Un, d_norm_pdz, kp);
         }
     }));
     CHK(launch_check(c, "k_row_pass"));
-    if (ll_blocks) *ll_blocks = grid;
+    if (ll_blocks) *ll_blocks = r.plan.grid;
     return 0;
 }
 
 // chunk boundaries of the column pass from the current fractions
 void balance_set_lo(plsa_ctx *c, int n_chunks) {
-    c->bal_lo[0] = 0;
-    for (int x = 1; x < 8; ++x) {
-        int v = (int)(c->bal_frac[x] * n_chunks + 0.5);
-        c->bal_lo[x] = std::min(n_chunks, std::max(c->bal_lo[x - 1], v));
-    }
-    c->bal_lo[8] = n_chunks;
+    plsa::plan::balance_lo(c->bal_frac, n_chunks, c->bal_lo);
     c->bal_chunks = n_chunks;
-}
-
-// Grid of the column pass: ONE chunk per workgroup (the dispatcher then walks each XCD's stretch strictly in list
-// order; with a capped grid a workgroup's later chunks lay a whole grid ahead of the window its XCD was working on:
-// 32 k / 64 k / 128 k workgroups at config 3 -> 1.86 / 1.83 / 1.79 ms).  With the XCD split every XCD gets grid / 8
-// workgroups, so the grid is eight times the longest stretch; the others' surplus workgroups exit at once.
-int col_grid(plsa_ctx *c, int n_chunks, bool split) {
-    i64 g = n_chunks;
-    if (split) {
-        int longest = 1;
-        for (int x = 0; x < 8; ++x) longest = std::max(longest, c->bal_lo[x + 1] - c->bal_lo[x]);
-        g = 8 * (i64)longest;
-    }
-    return (int)std::max<i64>(1, std::min<i64>(g, (i64)1 << 22));
 }
 
 // Measured XCD boundaries of the column pass (see k_col_pass).  `launch(timed)` enqueues one column pass on c->ls.
@@ -1219,7 +1187,7 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
     c->bal_launches = 0;
     // auto: corpora from ~1e8 cells per iteration (config 2: 4279 -> 4540 iterations/s; the tuning launches of a
     // 20NG-sized corpus would cost a bootstrap member more than they return)
-    // PLSA_SMALL_GRID caps the launch below col_grid(): workgroup b would no longer be chunk-stretch b's only visitor
+    // PLSA_SMALL_GRID caps the launch below plan::col_grid(): workgroup b would no longer be chunk-stretch b's only visitor
     // and the start stamp would land in a slot read as an end time -- that experiment knob runs on equal stretches
     const bool small_grid_active = c->small_grid > 0 && (double)c->nnz * c->kp < c->overlap_full_limit;
     const bool tune = split && n_chunks >= 64 && !small_grid_active &&
@@ -1233,7 +1201,7 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
         double best_spread = 1e300, best_frac[9];
         for (int x = 0; x <= 8; ++x) best_frac[x] = c->bal_frac[x];
         for (int it = 0; it < max_launches; ++it) {
-            const int grid = col_grid(c, n_chunks, split);
+            const int grid = plsa::plan::col_grid(c->bal_lo, n_chunks, split);
             te.assign((size_t)grid + 1, 0);
             HIPCHK(c, hipMemsetAsync(c->t_end.p, 0, sizeof(unsigned long long) * ((size_t)grid + 1), c->ls));
             CHK(launch(true));
@@ -1279,64 +1247,73 @@ int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
     return 0;
 }
 
+// What one column pass and its tail are launched with: the counterpart of RowLaunch, by the same rules (prepare_col_pass)
+struct ColLaunch {
+    plsa::plan::ColPass plan;
+    bool packed;                     // the packed entry stream
+    int xcd_split;                   // the pass walks its chunks in per-XCD stretches
+    const int4 *item_rec;            // item records in visiting order
+    i64 n_items;
+    const int *csc_row, *csc_pos;    // csc_row: the packed CSC stream when `packed`
+    const float *csc_val;
+    float *partial;                  // one k-vector per item
+    double *colsum_rows, *colsum_rows2;   // one float64 sum row per chunk; stage-2 rows of the norm (plan.norm_blocks of them)
+    float *norm_pwz;
+    const int *item_first, *heavy_cols;
+    int n_heavy, heavy_items;
+};
+
+int prepare_col_pass(plsa_ctx *c, bool from_p, ColLaunch &l) {
+    CHK(from_p ? ensure_csc(c) : ensure_packed_csc(c));
+    l.packed = !from_p && c->packed && c->pk_csc.ok;
+    l.plan = plsa::plan::col_pass(c->csc.n_items, c->m, c->lpn, c->csc.n_heavy, c->grid_cap);
+    l.xcd_split = plsa::plan::xcd_split(c->xcd_split, l.plan.n_chunks, c->n, c->kp) ? 1 : 0;
+    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->csc.n_items, 1) * c->kp));
+    CHK(ensure(c, c->colsum_rows, sizeof(double) * (size_t)std::max(l.plan.n_chunks, 1) * c->kp));
+    CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
+    if (l.plan.norm_blocks) CHK(ensure(c, c->colsum_rows2, sizeof(double) * (size_t)l.plan.norm_blocks * c->kp));
+    l.item_rec = c->csc.item_rec.as<int4>(); l.n_items = c->csc.n_items;
+    l.csc_row = l.packed ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
+    l.csc_pos = c->csc.pos.as<int>(); l.csc_val = c->csc.val.as<float>();
+    l.partial = c->partial.as<float>(); l.norm_pwz = c->norm_pwz.as<float>();
+    l.colsum_rows = c->colsum_rows.as<double>(); l.colsum_rows2 = c->colsum_rows2.as<double>();
+    l.item_first = c->csc.item_first.as<int>(); l.heavy_cols = c->csc.heavy_cols.as<int>();
+    l.n_heavy = c->csc.n_heavy; l.heavy_items = c->heavy_items;
+    return 0;
+}
+
 // vocabulary-owned pass (no atomics): partial k-vectors per column item (+ per-chunk sums of them, from
 // which the column tail gets norm_pwz), then per-column sums -> Vacc
 // parts: 1 = the column pass itself, 2 = the un-normalised per-column sums of its partials (k_col_reduce),
 //        3 = both
 int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int parts = 3) {
-    CHK(from_p ? ensure_csc(c) : ensure_packed_csc(c));
-    const bool packed = !from_p && c->packed && c->pk_csc.ok;
-    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->csc.n_items, 1) * c->kp));
+    ColLaunch l;
+    CHK(prepare_col_pass(c, from_p, l));
     int rc = 0;
     CHK(dispatch_shape_gather(c, table_is_wide(c, c->n), [&](auto S) {     // the pass gathers P(z|d) rows: n of them
         using Sh = decltype(S);
-        constexpr int LPN = Sh::LPN, GPB = 256 / LPN;
-        const i64 n_visit = c->csc.n_items;
-        const int n_chunks = (int)((n_visit + GPB - 1) / GPB);
-        const int grid2 = grid_for(c, c->m, GPB);
-        // a P(z|d) table that fits every XCD's L2 (20NG shape: 1.5 MB) has no band to keep local: plain grid-stride
-        // over the list, balanced by the dispatcher (config 1: 8990 -> 9490 iterations/s)
-        const bool u_fits_l2 = (double)c->n * c->kp * 4.0 <= 2.0 * 1024 * 1024;
-        const int xcd_split = (c->xcd_split && n_chunks >= 64 && !u_fits_l2) ? 1 : 0;
+        constexpr int GPB = 256 / Sh::LPN;
+        const int n_chunks = l.plan.n_chunks, kp = c->kp;
         if (parts & 1) {
-            c->fit_info.xcd_split = xcd_split;
-            rc = ensure(c, c->colsum_rows, sizeof(double) * (size_t)std::max(n_chunks, 1) * c->kp);
-            if (rc) return;
-            const size_t smem = sizeof(double) * (size_t)GPB * c->kp;
+            c->fit_info.xcd_split = l.xcd_split;
+            const size_t smem = sizeof(double) * (size_t)GPB * kp;
             auto launch = [&](bool timed) -> int {
-                int grid = col_grid(c, n_chunks, xcd_split != 0);
+                int grid = plsa::plan::col_grid(c->bal_lo, n_chunks, l.xcd_split != 0);
                 // PLSA_SMALL_GRID (experiment knob): cap the pass of a small corpus at that many workgroups per CU
-                if (c->small_grid > 0 && (double)c->nnz * c->kp < c->overlap_full_limit)
+                if (c->small_grid > 0 && (double)c->nnz * kp < c->overlap_full_limit)
                     grid = std::min(grid, c->small_grid * c->prop.multiProcessorCount);
                 Scope s(c, from_p ? "k_col_pass<P>" : "k_col_pass<fused>");
-                const int4 *rec = c->csc.item_rec.as<int4>();
-                const int *lo = c->csc.xcd_lo.as<int>(), *cp = c->csc.pos.as<int>();
-                const int *cr = packed ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
-                const float *cvl = c->csc.val.as<float>(), *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
-                float *part = c->partial.as<float>();
-                double *sums = c->colsum_rows.as<double>();
+                const int *lo = c->csc.xcd_lo.as<int>();
+                const float *U = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
                 unsigned long long *te = c->t_end.as<unsigned long long>();
-                const int kp = c->kp;
-                auto run = [&](auto SS, auto FP, auto TM, auto TN) {
+                select_col_pass<Sh>(l.packed, from_p, timed, thresh < plsa::TINY_THRESH, [&](auto SS, auto FP, auto TM, auto TN) {
                     hipLaunchKernelGGL((plsa::k_col_pass<decltype(SS), decltype(FP)::value, decltype(TM)::value, decltype(TN)::value>),
-                                       dim3(grid), dim3(256), smem, c->ls, rec, n_visit, lo, cr, cvl, cp, U, Vt, p_base(c), d_sw,
-                                       part, kp, thresh, xcd_split, sums, te);
-                };
-                auto go = [&](auto FP, auto TM, auto TN) {   // fused: the packed entry stream when it is eligible
-                    if constexpr (!decltype(FP)::value) {
-                        if (packed) { run(plsa::Packed<Sh>{}, FP, TM, TN); return; }
-                    }
-                    run(Sh{}, FP, TM, TN);
-                };
-                using T = std::true_type;
-                using F = std::false_type;
-                const bool tiny = !from_p && thresh < plsa::TINY_THRESH;
-                if (from_p) { if (timed) go(T{}, T{}, F{}); else go(T{}, F{}, F{}); }
-                else if (tiny) { if (timed) go(F{}, T{}, T{}); else go(F{}, F{}, T{}); }
-                else { if (timed) go(F{}, T{}, F{}); else go(F{}, F{}, F{}); }
+                                       dim3(grid), dim3(256), smem, c->ls, l.item_rec, l.n_items, lo, l.csc_row, l.csc_val, l.csc_pos,
+                                       U, Vt, p_base(c), d_sw, l.partial, kp, thresh, l.xcd_split, l.colsum_rows, te);
+                });
                 return launch_check(c, "k_col_pass");
             };
-            rc = ensure_balance(c, n_chunks, xcd_split != 0, launch);
+            rc = ensure_balance(c, n_chunks, l.xcd_split != 0, launch);
             if (rc) return;
             rc = launch(false);
             if (rc) return;
@@ -1345,10 +1322,8 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
         if (parts & 2) {
             // heavy columns (one block each) and the rest share one launch
             Scope s(c, "k_col_reduce");
-            hipLaunchKernelGGL((plsa::k_col_reduce<Sh>), dim3(grid2 + c->csc.n_heavy), dim3(256),
-                               (256 / LPN) * c->kp * sizeof(float), c->ls,
-                               c->csc.item_first.as<int>(), (int)c->m, c->heavy_items, c->csc.heavy_cols.as<int>(), c->csc.n_heavy,
-                               c->partial.as<float>(), c->Vacc.as<float>(), c->kp);
+            hipLaunchKernelGGL((plsa::k_col_reduce<Sh>), dim3(l.plan.reduce_grid), dim3(256), GPB * kp * sizeof(float), c->ls,
+                               l.item_first, (int)c->m, l.heavy_items, l.heavy_cols, l.n_heavy, l.partial, c->Vacc.as<float>(), kp);
         }
     }));
     if (rc) return rc;
@@ -1400,36 +1375,31 @@ int run_col_tail(plsa_ctx *c) {
         CHK(run_col_pass(c, false, nullptr, 0.f, 2));
         return run_v_normalise(c);
     }
+    ColLaunch l;
+    CHK(prepare_col_pass(c, true, l));           // (the tail reads no entry stream: nothing packed to ensure)
     c->fit_info.tail = 1;
-    c->fit_info.two_stage = c->colsum_rows_used > 2048;
-    const int rows = c->colsum_rows_used;
-    if (rows <= 0) return fail(c, "internal: column tail without a column pass");
-    CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
-    const double *rows_in = c->colsum_rows.as<double>();
-    int n_rows = rows;
-    if (rows > 2048) {               // many chunks (large corpora): two stages
-        const int nb = std::max(64, std::min(1024, rows / 64));
-        CHK(ensure(c, c->colsum_rows2, sizeof(double) * (size_t)nb * c->kp));
+    c->fit_info.two_stage = l.plan.norm_blocks > 0;
+    if (c->colsum_rows_used <= 0) return fail(c, "internal: column tail without a column pass");
+    const double *rows_in = l.colsum_rows;
+    int n_rows = l.plan.n_chunks;
+    if (l.plan.norm_blocks) {        // many chunks (large corpora): two stages
         Scope s(c, "k_norm_reduce");
-        hipLaunchKernelGGL(plsa::k_norm_reduce, dim3(nb), dim3(256), 0, c->ls, rows_in, rows, c->kp,
-                           c->colsum_rows2.as<double>());
-        rows_in = c->colsum_rows2.as<double>();
-        n_rows = nb;
+        hipLaunchKernelGGL(plsa::k_norm_reduce, dim3(l.plan.norm_blocks), dim3(256), 0, c->ls, rows_in, n_rows, c->kp,
+                           l.colsum_rows2);
+        rows_in = l.colsum_rows2;
+        n_rows = l.plan.norm_blocks;
     }
     {
         Scope s(c, "k_colsum_final");
-        hipLaunchKernelGGL(plsa::k_colsum_final, dim3(1), dim3(256), 0, c->ls, rows_in, n_rows, c->kp,
-                           c->norm_pwz.as<float>());
+        hipLaunchKernelGGL(plsa::k_colsum_final, dim3(1), dim3(256), 0, c->ls, rows_in, n_rows, c->kp, l.norm_pwz);
     }
     CHK(dispatch_shape(c, [&](auto S) {
         using Sh = decltype(S);
         constexpr int GPB = 256 / Sh::LPN;
-        const int grid2 = grid_for(c, c->m, GPB);
         Scope s(c, "k_col_reduce_norm");
-        hipLaunchKernelGGL((plsa::k_col_reduce_norm<Sh>), dim3(grid2 + c->csc.n_heavy), dim3(256),
-                           sizeof(float) * (size_t)(GPB + 1) * c->kp, c->ls, c->csc.item_first.as<int>(), (int)c->m,
-                           c->heavy_items, c->csc.heavy_cols.as<int>(), c->csc.n_heavy, c->partial.as<float>(),
-                           c->norm_pwz.as<float>(), c->Vt[out_v(c)].as<float>(), c->kp);
+        hipLaunchKernelGGL((plsa::k_col_reduce_norm<Sh>), dim3(l.plan.reduce_grid), dim3(256),
+                           sizeof(float) * (size_t)(GPB + 1) * c->kp, c->ls, l.item_first, (int)c->m, l.heavy_items, l.heavy_cols,
+                           l.n_heavy, l.partial, l.norm_pwz, c->Vt[out_v(c)].as<float>(), c->kp);
     }));
     return launch_check(c, "k_col_reduce_norm");
 }

@@ -2,9 +2,10 @@
 // translation unit (included at its end: it uses the context, the builders and the launch helpers defined there).
 //
 // Layout of a batch.  Every member slot is a plsa_ctx of its own that BORROWS the leader's streams and base corpus:
-// its resample, CSC items, packed streams, row items / row order, lane shape and factors are built by the code a
-// standalone fit runs (plsa_bootstrap, mt_init / plsa_set_factors, ensure_*), with the member's own n, nnz and kp -- so
-// item lengths, the row-item decision, heavy-column lists and chunk boundaries are the standalone ones by construction.
+// its resample, lane shape and factors are built by the code a standalone fit runs (plsa_bootstrap, mt_init /
+// plsa_set_factors), and its structures, scratch and grids come from the two preparations a standalone pass launches from
+// (prepare_col_pass, prepare_row_pass), with the member's own n, nnz and kp -- so item lengths, the row-item decision,
+// heavy-column lists, chunk counts and grids are the standalone ones by construction.
 // The builders' scratch (tmp0..2, cubtmp, the MT19937 words) is the LEADER's, lent for the duration of a call.
 // plsa_members_fit then groups the members by kernel instantiation (packed column stream, packed document stream), fills
 // one plsa::MemberArgs per member and runs the fused schedule with one launch per kernel and group
@@ -76,65 +77,48 @@ int members_check(plsa_members *b, int32_t member) {
     return 0;
 }
 
-// the structures and buffers of one member's fused iteration, as the standalone wrappers (run_row_pass, run_col_pass,
-// run_col_tail) ensure them, and the member's standalone grids -> one table row
+// one member's fused iteration -> one table row: the two preparations a standalone fit launches from (prepare_col_pass,
+// prepare_row_pass; every member's document pass may carry the likelihood), copied field by field
 int member_args(plsa_ctx *c, double *ll_out, plsa::MemberArgs &a, plsa_members::Info &inf) {
-    CHK(ensure_packed_csc(c));
-    CHK(ensure_packed_csr(c));
-    CHK(ensure_ritems(c));
-    const bool items = c->ritems.use && c->ritems.n > 0;
-    const int *order = nullptr;
-    if (!items) CHK(ensure_roworder(c, &order));
-    const int row_grid = grid_for(c, items ? c->ritems.n : c->n, 256 / c->row_lpn);
-    if (items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->ritems.n * c->kp));
-    CHK(ensure(c, c->ll_partials, sizeof(double) * (size_t)row_grid));
-    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->csc.n_items, 1) * c->kp));
-    const int gpb = 256 / c->lpn;
-    const int n_chunks = (int)((c->csc.n_items + gpb - 1) / gpb);
-    CHK(ensure(c, c->colsum_rows, sizeof(double) * (size_t)std::max(n_chunks, 1) * c->kp));
-    CHK(ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp));
-    int norm_blocks = 0;
-    if (n_chunks > 2048) {           // run_col_tail: two stages
-        norm_blocks = std::max(64, std::min(1024, n_chunks / 64));
-        CHK(ensure(c, c->colsum_rows2, sizeof(double) * (size_t)norm_blocks * c->kp));
-    }
-    const bool pk_col = c->packed && c->pk_csc.ok, pk_row = c->packed && c->pk_csr.ok;
+    ColLaunch l;
+    RowLaunch r;
+    CHK(prepare_col_pass(c, false, l));
+    CHK(prepare_row_pass(c, false, true, r));
     a = plsa::MemberArgs{};
-    a.item_rec = c->csc.item_rec.as<int4>();
-    a.csc_row = pk_col ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
-    a.csc_val = c->csc.val.as<float>();
-    a.partial = c->partial.as<float>();
-    a.chunk_sums = c->colsum_rows.as<double>();
-    a.n_items = c->csc.n_items;
-    a.chunk_sums2 = c->colsum_rows2.as<double>();
-    a.norm_pwz = c->norm_pwz.as<float>();
-    a.item_first = c->csc.item_first.as<int>();
-    a.heavy_cols = c->csc.heavy_cols.as<int>();
-    a.n_chunks = n_chunks;
-    a.norm_blocks = norm_blocks;
+    a.item_rec = l.item_rec;
+    a.csc_row = l.csc_row;
+    a.csc_val = l.csc_val;
+    a.partial = l.partial;
+    a.chunk_sums = l.colsum_rows;
+    a.n_items = l.n_items;
+    a.chunk_sums2 = l.colsum_rows2;
+    a.norm_pwz = l.norm_pwz;
+    a.item_first = l.item_first;
+    a.heavy_cols = l.heavy_cols;
+    a.n_chunks = l.plan.n_chunks;
+    a.norm_blocks = l.plan.norm_blocks;
     a.m = (int)c->m;
-    a.n_heavy = c->csc.n_heavy;
-    a.heavy_items = c->heavy_items;
-    a.reduce_grid = grid_for(c, c->m, gpb) + c->csc.n_heavy;
-    a.indptr = c->indptr;
-    a.colidx = pk_row ? c->pk_csr.buf.as<int>() : c->col;
-    a.vals = c->val;
-    a.row_order = order;
-    a.ritem_row = items ? c->ritems.row.as<int>() : nullptr;
-    a.ritem_start = items ? c->ritems.start.as<int>() : nullptr;
-    a.ritem_first = items ? c->ritems.first.as<int>() : nullptr;
-    a.rpartial = items ? c->rpartial.as<float>() : nullptr;
-    a.ll_partials = c->ll_partials.as<double>();
+    a.n_heavy = l.n_heavy;
+    a.heavy_items = l.heavy_items;
+    a.reduce_grid = l.plan.reduce_grid;
+    a.indptr = r.indptr;
+    a.colidx = r.colidx;
+    a.vals = r.vals;
+    a.row_order = r.order;
+    a.ritem_row = r.ritem_row;
+    a.ritem_start = r.ritem_start;
+    a.ritem_first = r.ritem_first;
+    a.rpartial = r.rpartial;
+    a.ll_partials = r.ll_partials;
     a.ll_out = ll_out;
-    a.n_ritems = c->ritems.n;
+    a.n_ritems = r.n_ritems;
     a.n = (int)c->n;
-    a.rseg = c->ritems.seg;
-    a.row_grid = row_grid;
-    a.row_reduce_grid = grid_for(c, c->n, 256 / c->row_lpn);
+    a.rseg = r.rseg;
+    a.row_grid = r.plan.grid;
+    a.row_reduce_grid = r.plan.reduce_grid;
     for (int i = 0; i < 2; ++i) { a.U[i] = c->U[i].as<float>(); a.Vt[i] = c->Vt[i].as<float>(); }
-    inf.items = items; inf.rseg = c->ritems.seg; inf.n_chunks = n_chunks; inf.n_heavy = c->csc.n_heavy;
-    inf.row_grid = row_grid; inf.norm_blocks = norm_blocks;
-    c->colsum_rows_used = n_chunks;
+    inf.items = r.items; inf.rseg = r.rseg; inf.n_chunks = l.plan.n_chunks; inf.n_heavy = l.n_heavy;
+    inf.row_grid = r.plan.grid; inf.norm_blocks = l.plan.norm_blocks;
     return 0;
 }
 
@@ -175,8 +159,7 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
         if (c->cu) cu |= 1ull << g;
         if (c->cv) cv |= 1ull << g;
     }
-    using T = std::true_type;
-    using F = std::false_type;
+    using F = std::false_type;           // a batch is fused and untimed: those two choices are fixed
     // The two halves of an iteration read the same current factors and write disjoint outputs: the column chain runs on
     // the leader's second stream underneath the document pass (fork / join per iteration, like plsa_fit's small-corpus form)
     const bool two_streams = L->overlap;
@@ -184,13 +167,10 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
     auto row_pass = [&](bool want_ll) -> int {
         CHK(dispatch_narrow_row(c0, [&](auto S) {
             using Sh = decltype(S);
-            auto launch = [&](auto SS, auto LL, auto TN) {
+            select_row_pass<Sh>(pk_row, F{}, want_ll, tiny, [&](auto SS, auto, auto LL, auto TN) {
                 hipLaunchKernelGGL((plsa::k_row_pass_members<decltype(SS), decltype(LL)::value, decltype(TN)::value>),
                                    dim3(row_x, G), dim3(256), 0, L->stream, table, live, cu, cv, kp, thresh);
-            };
-            auto go = [&](auto LL, auto TN) { if (pk_row) launch(plsa::Packed<Sh>{}, LL, TN); else launch(Sh{}, LL, TN); };
-            if (want_ll) { if (tiny) go(T{}, T{}); else go(T{}, F{}); }
-            else { if (tiny) go(F{}, T{}); else go(F{}, F{}); }
+            });
             if (rr_x > 0)
                 hipLaunchKernelGGL((plsa::k_row_reduce_members<Sh>), dim3(rr_x, G), dim3(256), 0, L->stream, table, live, cu, kp);
         }));
@@ -205,12 +185,10 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
             using Sh = decltype(S);
             constexpr int GPB = 256 / Sh::LPN;
             const size_t smem = sizeof(double) * (size_t)GPB * kp;
-            auto launch = [&](auto SS, auto TN) {
+            select_col_pass<Sh>(pk_col, F{}, F{}, tiny, [&](auto SS, auto, auto, auto TN) {
                 hipLaunchKernelGGL((plsa::k_col_pass_members<decltype(SS), decltype(TN)::value>), dim3(chunks_x, G), dim3(256),
                                    smem, col_stream, table, live, cu, cv, kp, thresh);
-            };
-            auto go = [&](auto TN) { if (pk_col) launch(plsa::Packed<Sh>{}, TN); else launch(Sh{}, TN); };
-            if (tiny) go(T{}); else go(F{});
+            });
             if (norm_x > 0)
                 hipLaunchKernelGGL(plsa::k_norm_reduce_members, dim3(norm_x, G), dim3(256), 0, col_stream, table, live, kp);
             hipLaunchKernelGGL(plsa::k_colsum_final_members, dim3(G), dim3(256), 0, col_stream, table, live, kp);

@@ -2,9 +2,9 @@
 // (included at its end: it uses the context, the builders and the launch helpers defined there).
 //
 // W lives in U[cu], H in Vt[cv]; both halves update in place (a document's row is read and written by its own group, the
-// H tail is elementwise), so cu / cv never move and the alternates stay free.  The structures are the EM passes': row
-// order / row items and the packed CSR stream for the document pass, the CSC items and their packed stream for the
-// column pass, `partial` and `Vacc` for the per-item and per-column sums (k_col_reduce adds them, heavy columns included).
+// H tail is elementwise), so cu / cv never move and the alternates stay free.  The structures, entry streams, scratch and
+// grids are the EM passes', taken from their preparations (prepare_row_pass, prepare_col_pass); `Vacc` holds the per-column
+// sums (k_col_reduce adds the item partials, heavy columns included).
 #pragma once
 
 namespace {
@@ -42,35 +42,25 @@ bool nmf_row_items(plsa_ctx *c) { return c->ritems.use && c->ritems.n > 0; }
 
 // `iters` W half-iterations with H (and the H_sum already on the device) fixed; more than one only in row-ordered mode
 int nmf_run_update_w(plsa_ctx *c, int iters) {
-    CHK(ensure_ritems(c));
-    const bool items = nmf_row_items(c);
-    if (items && iters != 1) return fail(c, "internal: the combined NMF pass needs whole documents");
-    const int *order = nullptr;
-    if (!items) CHK(ensure_roworder(c, &order));
-    if (items) CHK(ensure(c, c->rpartial, sizeof(float) * (size_t)c->ritems.n * c->kp));
-    CHK(ensure_packed_csr(c));
-    const bool packed = c->packed && c->pk_csr.ok;
-    const int grid = grid_for(c, items ? c->ritems.n : c->n, 256 / c->row_lpn);
+    RowLaunch r;
+    CHK(prepare_row_pass(c, false, false, r));
+    if (r.items && iters != 1) return fail(c, "internal: the combined NMF pass needs whole documents");
     c->p_state.invalidate();
     CHK(dispatch_shape_row(c, [&](auto S) {
         using Sh = decltype(S);
-        const int *ip = c->indptr, *cl = packed ? c->pk_csr.buf.as<int>() : c->col;
-        const float *vl = c->val, *Vt = c->Vt[c->cv].as<float>(), *hs = c->nmf.guarded.as<float>() + c->kp;
+        const float *Vt = c->Vt[c->cv].as<float>(), *hs = c->nmf.guarded.as<float>() + c->kp;
         float *W = c->U[c->cu].as<float>();
-        const int *ri_row = items ? c->ritems.row.as<int>() : nullptr, *ri_start = items ? c->ritems.start.as<int>() : nullptr;
-        float *rpart = items ? c->rpartial.as<float>() : nullptr;
-        const int n = (int)c->n, kp = c->kp, rseg = c->ritems.seg;
-        const i64 n_ritems = c->ritems.n;
+        const int n = (int)c->n, kp = c->kp;
         auto launch = [&](auto SS) {
             Scope s(c, "k_nmf_row_pass");
-            hipLaunchKernelGGL((plsa::k_nmf_row_pass<decltype(SS)>), dim3(grid), dim3(256), 0, c->ls, ip, cl, vl, n, order, W, Vt,
-                               hs, kp, iters, ri_row, ri_start, rseg, n_ritems, rpart);
+            hipLaunchKernelGGL((plsa::k_nmf_row_pass<decltype(SS)>), dim3(r.plan.grid), dim3(256), 0, c->ls, r.indptr, r.colidx,
+                               r.vals, n, r.order, W, Vt, hs, kp, iters, r.ritem_row, r.ritem_start, r.rseg, r.n_ritems, r.rpartial);
         };
-        if (packed) launch(plsa::Packed<Sh>{}); else launch(Sh{});
-        if (items) {
+        if (r.packed) launch(plsa::Packed<Sh>{}); else launch(Sh{});
+        if (r.items) {
             Scope s(c, "k_nmf_row_reduce");
-            hipLaunchKernelGGL((plsa::k_nmf_row_reduce<Sh>), dim3(grid_for(c, c->n, 256 / Sh::LPN)), dim3(256), 0, c->ls,
-                               c->ritems.first.as<int>(), n, rpart, W, hs, kp);
+            hipLaunchKernelGGL((plsa::k_nmf_row_reduce<Sh>), dim3(r.plan.reduce_grid), dim3(256), 0, c->ls,
+                               r.ritem_first, n, r.rpartial, W, hs, kp);
         }
     }));
     return launch_check(c, "k_nmf_row_pass");
@@ -78,27 +68,20 @@ int nmf_run_update_w(plsa_ctx *c, int iters) {
 
 // one H half-iteration from the current W: W_sum, the column pass, the per-column sums, the update
 int nmf_run_update_h(plsa_ctx *c) {
-    CHK(ensure_packed_csc(c));
-    const bool packed = c->packed && c->pk_csc.ok;
-    CHK(ensure(c, c->partial, sizeof(float) * (size_t)std::max<i64>(c->csc.n_items, 1) * c->kp));
+    ColLaunch l;
+    CHK(prepare_col_pass(c, false, l));
     CHK(nmf_factor_sum(c, 0));
     c->p_state.invalidate();
     CHK(dispatch_shape_gather(c, table_is_wide(c, c->n), [&](auto S) {     // the pass gathers W rows: n of them
         using Sh = decltype(S);
-        constexpr int GPB = 256 / Sh::LPN;
-        const i64 n_items = c->csc.n_items;
-        const int grid = (int)std::max<i64>(1, std::min<i64>((n_items + GPB - 1) / GPB, (i64)1 << 22));
-        const int4 *rec = c->csc.item_rec.as<int4>();
-        const int *cr = packed ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
-        const float *cvl = c->csc.val.as<float>(), *W = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
-        float *part = c->partial.as<float>();
-        const int kp = c->kp;
+        const int grid = plsa::plan::col_grid(nullptr, l.plan.n_chunks, false);      // one chunk per workgroup, no XCD stretches
+        const float *W = c->U[c->cu].as<float>(), *Vt = c->Vt[c->cv].as<float>();
         auto launch = [&](auto SS) {
             Scope s(c, "k_nmf_col_pass");
-            hipLaunchKernelGGL((plsa::k_nmf_col_pass<decltype(SS)>), dim3(grid), dim3(256), 0, c->ls, rec, n_items, cr, cvl, W, Vt,
-                               part, kp);
+            hipLaunchKernelGGL((plsa::k_nmf_col_pass<decltype(SS)>), dim3(grid), dim3(256), 0, c->ls, l.item_rec, l.n_items,
+                               l.csc_row, l.csc_val, W, Vt, l.partial, c->kp);
         };
-        if (packed) launch(plsa::Packed<Sh>{}); else launch(Sh{});
+        if (l.packed) launch(plsa::Packed<Sh>{}); else launch(Sh{});
     }));
     CHK(launch_check(c, "k_nmf_col_pass"));
     CHK(run_col_pass(c, false, nullptr, 0.f, 2));          // k_col_reduce: partial -> Vacc, fixed item order
@@ -111,17 +94,20 @@ int nmf_run_update_h(plsa_ctx *c) {
     return launch_check(c, "k_nmf_h_finish");
 }
 
+// the objective walks whole documents in the document pass' lane shape: that pass' two arrays and its whole-document grid
 int nmf_run_divergence(plsa_ctx *c, double *out) {
     CHK(nmf_factor_sum(c, 0));
     CHK(nmf_factor_sum(c, 1));
-    const int grid = grid_for(c, c->n, 256 / c->row_lpn);
-    const int *order = nullptr;
-    CHK(ensure_roworder(c, &order));
+    RowLaunch r;
+    CHK(prepare_row_pass(c, true, false, r));
+    const int grid = r.plan.reduce_grid;
+    const int *order = r.order;
+    if (r.items) CHK(ensure_roworder(c, &order));          // (a pass over row items has no use for the order)
     CHK(ensure(c, c->nmf.obj, sizeof(double) * 2 * (size_t)grid));
     CHK(ensure(c, c->nmf.out, sizeof(double) * 2));
     CHK(dispatch_shape_row(c, [&](auto S) {
         Scope s(c, "k_nmf_divergence");
-        hipLaunchKernelGGL((plsa::k_nmf_divergence<decltype(S)>), dim3(grid), dim3(256), 0, c->ls, c->indptr, c->col, c->val,
+        hipLaunchKernelGGL((plsa::k_nmf_divergence<decltype(S)>), dim3(grid), dim3(256), 0, c->ls, r.indptr, r.colidx, r.vals,
                            (int)c->n, order, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), c->kp, c->nmf.obj.as<double>());
     }));
     {
