@@ -970,19 +970,10 @@ int need_factors(plsa_ctx *c) {
 // ---------------------------------------------------------------------------------------------
 // kernel wrappers
 // ---------------------------------------------------------------------------------------------
-// a block of documents of the budgeted reference arithmetic: entries [e0, e0 + nnz) of the COO order, documents [d0, d1)
-struct RefSpan {
-    i64 e0, nnz;
-    int d0, d1;
-    i64 cap;           // non-zeros of the plan's largest block: scratch is sized once for all blocks
-    bool first, last;
-};
-int run_ref_e_step(plsa_ctx *c, float thresh, const RefSpan *span = nullptr);
-int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw, const RefSpan *span = nullptr);
-int ensure_ref_heavy(plsa_ctx *c);
-bool ref_pairs_now(const plsa_ctx *c);
-int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz);
-int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out);
+// Compile-time choices of a pass' instantiation.  A bool picks its tag at run time; a caller that fixes a choice passes the
+// tag itself (std::false_type{}) and only that branch is instantiated.
+template <class Fn> void with_flag(bool v, Fn &&fn) { if (v) fn(std::true_type{}); else fn(std::false_type{}); }
+template <bool V, class Fn> void with_flag(std::integral_constant<bool, V> v, Fn &&fn) { fn(v); }
 
 // P(z|w,d) for `rows` non-zeros (all of them, or the largest block of a budgeted reference-arithmetic iteration)
 int ensure_p(plsa_ctx *c, i64 rows) {
@@ -1017,6 +1008,12 @@ int ensure_p(plsa_ctx *c, i64 rows) {
     }
     return 0;
 }
+
+}  // namespace
+
+#include "plsa_ref.hpp"       // the reference arithmetic (PLSA_REFERENCE_SUMS / PLSA_REFERENCE_LL): E-step, M-step, blocks, likelihood
+
+namespace {
 
 int run_e_step(plsa_ctx *c, float thresh) {
     c->ref_tsum.invalidate();          // (a new P(z|w,d): the tile sums of the last reference-arithmetic E-step are history)
@@ -1066,11 +1063,6 @@ int run_e_step(plsa_ctx *c, float thresh) {
     c->p_state.valid = true;
     return 0;
 }
-
-// Compile-time choices of a pass' instantiation.  A bool picks its tag at run time; a caller that fixes a choice passes the
-// tag itself (std::false_type{}) and only that branch is instantiated.
-template <class Fn> void with_flag(bool v, Fn &&fn) { if (v) fn(std::true_type{}); else fn(std::false_type{}); }
-template <bool V, class Fn> void with_flag(std::integral_constant<bool, V> v, Fn &&fn) { fn(v); }
 
 // Instantiation of the document pass in lane shape Sh: fn(stream shape, FROM_P, LL, TINY).  Fused: the packed entry stream
 // when it is eligible; TINY: the denormal-norm rescue, compiled in for thresholds below TINY_THRESH only.  From P(z|w,d):
@@ -1458,477 +1450,6 @@ int run_m_step_from_p(plsa_ctx *c, const float *d_sw, bool update_v, float *d_no
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// reference arithmetic (plsa_ref_kernels.hpp): the reference's statements with the reference's roundings
-// ---------------------------------------------------------------------------------------------
-// lanes per document / column (G) and topics per lane (NZ) of the reference-arithmetic passes: z = lane + G t
-template <class Fn>
-int dispatch_ref_group(plsa_ctx *c, Fn &&fn) {
-    using std::integral_constant;
-    const int kp = c->kp;
-    if (kp <= 8) fn(integral_constant<int, 8>{}, integral_constant<int, 1>{});
-    else if (kp <= 16) fn(integral_constant<int, 16>{}, integral_constant<int, 1>{});
-    else if (kp <= 32) fn(integral_constant<int, 32>{}, integral_constant<int, 1>{});
-    else if (kp <= 64) fn(integral_constant<int, 64>{}, integral_constant<int, 1>{});
-    else if (kp <= 128) fn(integral_constant<int, 64>{}, integral_constant<int, 2>{});
-    else if (kp <= 256) fn(integral_constant<int, 64>{}, integral_constant<int, 4>{});
-    else if (kp <= 512) fn(integral_constant<int, 64>{}, integral_constant<int, 8>{});
-    else if (kp <= 1024) fn(integral_constant<int, 64>{}, integral_constant<int, 16>{});
-    else return fail(c, "unsupported topic count k=%d (max 1024)", c->k);
-    return 0;
-}
-
-// plsa.py:91-105 with one float32 norm per entry, topics in order (P allocated by run_e_step); span: the entries of one block of
-// documents into the block's P (allocated by run_ref_em_blocked)
-int run_ref_e_step(plsa_ctx *c, float thresh, const RefSpan *span) {
-    CHK(ensure_rowidx(c));
-    const i64 e0 = span ? span->e0 : 0, nnz = span ? span->nnz : c->nnz;
-    const int *ri = c->rowidx.ids.as<int>() + e0, *ci = c->col + e0;
-    const float *xv = c->val + e0;
-    static const bool tiled = [] { const char *e = getenv("PLSA_REF_E_TILED"); return !e || atoi(e) != 0; }();
-    if (tiled && nnz > 0) {
-        Scope s(c, "k_ref_e_step");
-        const int kp = c->kp;
-        // (PLSA_REF_FUSE_SUMS=0: no tile sums, the chain's k_ref_pair_sums reads P itself)
-        const char *fe = getenv("PLSA_REF_FUSE_SUMS");
-        const bool fuse = (!fe || atoi(fe) != 0) && ref_pairs_now(c) && !c->ref_e_no_sums;
-        int rc_alloc = 0;
-        auto go = [&](auto NZ) {
-            constexpr int nz = decltype(NZ)::value;
-            const i64 tiles = (nnz + 64 / nz - 1) / (64 / nz);
-            const i64 cap_tiles = span ? (span->cap + 64 / nz - 1) / (64 / nz) : tiles;     // (blocks: sized once, for the largest)
-            if (fuse && (rc_alloc = ensure(c, c->ref_tsum.sums, sizeof(float) * (size_t)cap_tiles * kp)) == 0) {
-                hipLaunchKernelGGL((plsa::ref::k_ref_e_step_tiled<nz, true>), dim3(grid_for(c, tiles, 2)), dim3(128),
-                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, ri, ci, nnz,
-                                   c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, xv, c->ref_e_sw,
-                                   c->ref_tsum.sums.as<float>());
-                c->ref_tsum.valid = true; c->ref_tsum.sw = c->ref_e_sw; c->ref_tsum.tj = 64 / nz;
-            } else if (!rc_alloc) {
-                hipLaunchKernelGGL((plsa::ref::k_ref_e_step_tiled<nz, false>), dim3(grid_for(c, tiles, 2)), dim3(128),
-                                   sizeof(float) * 2 * (64 / nz) * (size_t)(kp + 1), c->stream, ri, ci, nnz,
-                                   c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(), p_base(c), kp, thresh, nullptr, nullptr, nullptr);
-            }
-        };
-        using std::integral_constant;
-        if (kp <= 64) go(integral_constant<int, 1>{});
-        else if (kp <= 128) go(integral_constant<int, 2>{});
-        else if (kp <= 256) go(integral_constant<int, 4>{});
-        else if (kp <= 512) go(integral_constant<int, 8>{});
-        else go(integral_constant<int, 16>{});
-        if (rc_alloc) return rc_alloc;
-    } else {
-        Scope s(c, "k_ref_e_step");
-        hipLaunchKernelGGL(plsa::ref::k_ref_e_step, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
-                           ri, ci, nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
-                           p_base(c), c->kp, thresh);
-    }
-    CHK(launch_check(c, "k_ref_e_step"));
-    c->p_state.valid = true;
-    return 0;
-}
-
-// norm_pwz[z] = the reference's ONE float32 running sum over all non-zeros (plsa.py:193) on c->ls: from per-chunk parity pairs and a
-// walk (k_ref_pair_*), or by the serial chain (k_ref_norm_chain); same bits either way.
-// the reference arithmetic's long columns (PLSA_REF_HEAVY_MIN entries or more, default 2048; 0: none): list [count, columns...]
-int ensure_ref_heavy(plsa_ctx *c) {
-    if (c->ref_heavy.valid) return 0;
-    const char *e = getenv("PLSA_REF_HEAVY_MIN");
-    c->ref_heavy.min = e ? atoi(e) : 2048;
-    c->ref_heavy.n = 0;
-    if (c->ref_heavy.min > 0 && c->nnz > 0) {
-        CHK(ensure(c, c->ref_heavy.cols, sizeof(int) * (size_t)(c->m + 1)));
-        HIPCHK(c, hipMemsetAsync(c->ref_heavy.cols.p, 0, sizeof(int), c->stream));
-        hipLaunchKernelGGL(plsa::ref::k_ref_heavy_cols, dim3((unsigned)((c->m + 255) / 256)), dim3(256), 0, c->stream,
-                           c->csc.colptr.as<int>(), (int)c->m, c->ref_heavy.min, c->ref_heavy.cols.as<int>() + 1, c->ref_heavy.cols.as<int>());
-        CHK(launch_check(c, "k_ref_heavy_cols"));
-        int n = 0;
-        HIPCHK(c, hipMemcpyAsync(&n, c->ref_heavy.cols.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ref_heavy.n = n;
-    }
-    c->ref_heavy.valid = true;
-    return 0;
-}
-
-// One chain of float32 additions over the non-zeros in order, per "topic" z < kp, WITHOUT the chain (plsa_ref_kernels.hpp: chunk
-// sums -> prefix -> (parity -> increment) pairs -> one checking walk per 64 topics), on c->ls.  kind / P / kp: PAIR_PLAIN or
-// PAIR_WEIGHTED over P(z|w,d) (norm_pwz, plsa.py:193), PAIR_NEG_TERMS over the likelihood terms with kp = 1 (plsa.py:322).
-// span: the entries of one block of documents, P the block's rows; a block after the first starts its chains from `out`.
-int run_ref_pair_chain(plsa_ctx *c, int kind, const float *P, int kp, const float *d_sw, float *out, unsigned long long *stats,
-                       const RefSpan *span = nullptr) {
-    const i64 e0 = span ? span->e0 : 0, nnz = span ? span->nnz : c->nnz, cap = span ? span->cap : c->nnz;
-    const bool carry = span && !span->first;
-    const int *ri = c->rowidx.ids.as<int>() + e0;
-    const float *xv = c->val + e0;
-    const bool ll = kind == plsa::ref::PAIR_NEG_TERMS;              // (timing names: the likelihood's launches apart from norm_pwz's)
-    // two levels (default): chunks of 256 addends, walked in groups of PAIR_R; PLSA_REF_LEVELS=1: chunks only, longer on large corpora
-    bool two = true;
-    if (const char *e = getenv("PLSA_REF_LEVELS")) two = atoi(e) != 1;
-    int L = !two && c->nnz >= plsa::ref::PAIR_L_LARGE_FROM ? plsa::ref::PAIR_L_LARGE : plsa::ref::PAIR_L_SMALL;
-    if (const char *e = getenv("PLSA_REF_CHUNK")) { const int v = atoi(e); if (v >= 64 && v <= 4096 && v % 64 == 0) L = v; }
-    const i64 n_chunks = (nnz + L - 1) / L;
-    const i64 n_groups = (n_chunks + plsa::ref::PAIR_R - 1) / plsa::ref::PAIR_R;
-    const i64 n_super = (n_chunks + plsa::ref::PAIR_SC - 1) / plsa::ref::PAIR_SC, n_pad = n_super * plsa::ref::PAIR_SC;
-    {   // scratch for the largest span this is called with (blocks: sized once, no reallocation under the chain of the block before)
-        const i64 cap_chunks = (cap + L - 1) / L, cap_groups = (cap_chunks + plsa::ref::PAIR_R - 1) / plsa::ref::PAIR_R;
-        const i64 cap_pad = (cap_chunks + plsa::ref::PAIR_SC - 1) / plsa::ref::PAIR_SC * plsa::ref::PAIR_SC;
-        if (two) {
-            CHK(ensure(c, c->ref_pairs2, sizeof(uint4) * (size_t)cap_groups * kp));
-            CHK(ensure(c, c->ref_exps2, sizeof(unsigned) * (size_t)cap_groups * kp));
-        }
-        CHK(ensure(c, c->ref_csum, sizeof(double) * (size_t)cap_pad * kp));
-        CHK(ensure(c, c->ref_pairs, sizeof(uint4) * (size_t)cap_chunks * kp));
-        CHK(ensure(c, c->ref_exps, sizeof(unsigned) * (size_t)cap_chunks * kp));
-    }
-    const int grid = grid_for(c, n_super, 4);
-    double *csum = c->ref_csum.as<double>();
-    uint4 *prs = c->ref_pairs.as<uint4>();
-    unsigned *exps = c->ref_exps.as<unsigned>();
-    auto by_nz = [&](auto &&go) {
-        using std::integral_constant;
-        if (kp <= 64) go(integral_constant<int, 1>{});
-        else if (kp <= 128) go(integral_constant<int, 2>{});
-        else if (kp <= 256) go(integral_constant<int, 4>{});
-        else if (kp <= 512) go(integral_constant<int, 8>{});
-        else go(integral_constant<int, 16>{});
-    };
-    by_nz([&](auto NZ) {
-        constexpr int nz = decltype(NZ)::value;
-        auto go = [&](auto KIND) {
-            constexpr int kd = decltype(KIND)::value;
-            if (!ll && c->ref_tsum.valid && c->ref_tsum.sw == d_sw && P == p_base(c) && c->p_state.valid && L % c->ref_tsum.tj == 0) {
-                // the E-step that wrote this P left the sums of its tiles: no second pass over P
-                Scope s(c, "k_ref_pair_sums");
-                const i64 n_tiles = (nnz + c->ref_tsum.tj - 1) / c->ref_tsum.tj;
-                hipLaunchKernelGGL(plsa::ref::k_ref_pair_sums_from_tiles, dim3(grid_for(c, n_chunks * kp, 256)), dim3(256), 0, c->ls,
-                                   c->ref_tsum.sums.as<float>(), kp, L / c->ref_tsum.tj, n_tiles, n_chunks, n_pad, csum);
-            } else {
-                Scope s(c, ll ? "k_ref_ll_pair_sums" : "k_ref_pair_sums");
-                hipLaunchKernelGGL((plsa::ref::k_ref_pair_sums<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, xv, nnz, P,
-                                   d_sw, kp, L, n_chunks, n_pad, csum);
-            }
-            {
-                Scope s(c, ll ? "k_ref_ll_pair_prefix" : "k_ref_pair_prefix");
-                if (carry) hipLaunchKernelGGL(plsa::ref::k_ref_pair_prefix<true>, dim3(kp), dim3(256), 0, c->ls, csum, n_chunks, n_pad, out);
-                else hipLaunchKernelGGL(plsa::ref::k_ref_pair_prefix<false>, dim3(kp), dim3(256), 0, c->ls, csum, n_chunks, n_pad, nullptr);
-            }
-            {
-                Scope s(c, ll ? "k_ref_ll_pair_build" : "k_ref_pair_build");
-                hipLaunchKernelGGL((plsa::ref::k_ref_pair_build<nz, kd>), dim3(grid), dim3(256), 0, c->ls, ri, xv, nnz, P,
-                                   d_sw, kp, L, n_chunks, n_pad, csum, prs, exps);
-            }
-            if (two) {
-                {
-                    Scope s(c, ll ? "k_ref_ll_pair_compose" : "k_ref_pair_compose");
-                    hipLaunchKernelGGL(plsa::ref::k_ref_pair_compose, dim3(grid_for(c, n_groups * kp, 256)), dim3(256), 0, c->ls, prs, exps,
-                                       kp, n_chunks, n_groups, c->ref_pairs2.as<uint4>(), c->ref_exps2.as<unsigned>());
-                }
-                Scope s(c, ll ? "k_ref_ll_pair_walk" : "k_ref_pair_walk");
-                auto walk = [&](auto CARRY) {
-                    hipLaunchKernelGGL((plsa::ref::k_ref_pair_walk<kd, true, decltype(CARRY)::value>), dim3((kp + 63) / 64),
-                                       dim3(plsa::ref::WALK_THREADS), 0, c->ls, ri, xv, nnz, P, d_sw, kp, L, n_groups,
-                                       c->ref_pairs2.as<uint4>(), c->ref_exps2.as<unsigned>(), out, stats, n_chunks, prs, exps);
-                };
-                if (carry) walk(std::true_type{}); else walk(std::false_type{});
-            } else {
-                Scope s(c, ll ? "k_ref_ll_pair_walk" : "k_ref_pair_walk");
-                auto walk = [&](auto CARRY) {
-                    hipLaunchKernelGGL((plsa::ref::k_ref_pair_walk<kd, false, decltype(CARRY)::value>), dim3((kp + 63) / 64),
-                                       dim3(plsa::ref::WALK_THREADS), 0, c->ls, ri, xv, nnz, P, d_sw, kp, L, n_chunks, prs, exps, out,
-                                       stats, n_chunks, prs, exps);
-                };
-                if (carry) walk(std::true_type{}); else walk(std::false_type{});
-            }
-        };
-        using std::integral_constant;
-        if (kind == plsa::ref::PAIR_NEG_TERMS) {
-            if constexpr (nz == 1) go(integral_constant<int, plsa::ref::PAIR_NEG_TERMS>{});      // (kp = 1)
-        } else if (kind == plsa::ref::PAIR_WEIGHTED) go(integral_constant<int, plsa::ref::PAIR_WEIGHTED>{});
-        else go(integral_constant<int, plsa::ref::PAIR_PLAIN>{});
-    });
-    return launch_check(c, "k_ref_pair_walk");
-}
-
-// does this context evaluate its long chains from parity pairs right now? (PLSA_REF_CHAIN; auto: from 4096 non-zeros, until a
-// finished walk reported more than a quarter of its chunks on the slow way)
-bool ref_pairs_now(const plsa_ctx *c) {
-    return c->ref_chain_mode == 1 || (c->ref_chain_mode == 0 && !c->ref_pairs_off && c->nnz >= 4096);
-}
-
-// span: the chain over one block's entries, started (after the first block) from what norm_pwz holds; the walk's counts add up
-// over the blocks and are read back after the last.
-int run_ref_norm_pwz(plsa_ctx *c, const float *d_sw, const RefSpan *span) {
-    const int kp = c->kp;
-    const i64 e0 = span ? span->e0 : 0, nnz = span ? span->nnz : c->nnz;
-    const bool carry = span && !span->first, last = !span || span->last;
-    const int *ri = c->rowidx.ids.as<int>() + e0;
-    const float *xv = c->val + e0;
-    float *out = c->norm_pwz.as<float>();
-    if (c->nnz <= 0) { HIPCHK(c, hipMemsetAsync(out, 0, sizeof(float) * (size_t)kp, c->ls)); return 0; }
-    // the last walk's count of slow chunks, if it has arrived (never waited for)
-    if (c->ref_stats_pending && hipEventQuery(c->ev_ref_stats) == hipSuccess) {
-        c->ref_stats_pending = false;
-        const unsigned long long slow = c->h_ref_stats[0], chunks = c->h_ref_stats[1];
-        c->ref_slow_total += slow; c->ref_chunks_total += chunks;
-        if (c->ref_chain_mode == 0 && chunks > 0 && slow * 4 > chunks) c->ref_pairs_off = true;
-    }
-    const bool pairs = ref_pairs_now(c);
-    auto by_nz = [&](auto &&go) {
-        using std::integral_constant;
-        if (kp <= 64) go(integral_constant<int, 1>{});
-        else if (kp <= 128) go(integral_constant<int, 2>{});
-        else if (kp <= 256) go(integral_constant<int, 4>{});
-        else if (kp <= 512) go(integral_constant<int, 8>{});
-        else go(integral_constant<int, 16>{});
-    };
-    if (!pairs) {
-        Scope s(c, "k_ref_norm_chain");
-        by_nz([&](auto NZ) {
-            auto go = [&](auto SW, auto CARRY) {
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<decltype(NZ)::value, decltype(SW)::value, false, decltype(CARRY)::value>),
-                                   dim3(1), dim3(plsa::ref::CHAIN_THREADS), 0, c->ls, ri, xv, nnz, p_base(c), d_sw, kp, out,
-                                   nullptr, nullptr, nullptr, (i64)0, (i64)0, 0);
-            };
-            if (d_sw) { if (carry) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
-            else { if (carry) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
-        });
-        return launch_check(c, "k_ref_norm_chain");
-    }
-    CHK(ensure(c, c->ref_stats, 32));
-    if (!c->h_ref_stats) {
-        HIPCHK(c, host_alloc(c->h_ref_stats, 2));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_ref_stats.h, hipEventDisableTiming));
-    }
-    unsigned long long *stats = c->ref_stats.as<unsigned long long>();
-    if (!carry) HIPCHK(c, hipMemsetAsync(stats, 0, 16, c->ls));
-    CHK(run_ref_pair_chain(c, d_sw ? plsa::ref::PAIR_WEIGHTED : plsa::ref::PAIR_PLAIN, p_base(c), kp, d_sw, out, stats, span));
-    CHK(launch_check(c, "k_ref_pair_walk"));
-    if (last && !c->ref_stats_pending) {       // (one read-back in flight at a time; a walk whose count is skipped is simply not counted)
-        HIPCHK(c, hipMemcpyAsync(c->h_ref_stats.get(), stats, 16, hipMemcpyDeviceToHost, c->ls));
-        HIPCHK(c, hipEventRecord(c->ev_ref_stats, c->ls));
-        c->ref_stats_pending = true;
-    }
-    return 0;
-}
-
-// The document pass, the column pass and the long columns of the reference M-step on c->stream, from the P(z|w,d) of all
-// non-zeros or (span) of one block of documents: that block's documents, and every column's entries inside the block with the
-// accumulators carried in Vacc from block to block.
-// (order: the length-sorted document order of the whole corpus; a block walks its documents in their own order)
-int run_ref_passes(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz, int heavy_min, const int *order,
-                   const RefSpan *span = nullptr) {
-    const int d0 = span ? span->d0 : 0, nd = span ? span->d1 - span->d0 : (int)c->n, first = !span || span->first;
-    const i64 e0 = span ? span->e0 : 0, e1 = span ? span->e0 + span->nnz : 0;
-    // the tiled document pass pays from ~300 k documents on (config 3 whole: 22 -> 10 ms); below, the wave tile that holds the few
-    // longest documents is the pass, and the group kernel walks a long document faster (PLSA_REF_ROW_TILED=1 / 0 pins either)
-    const char *row_tiled_env = getenv("PLSA_REF_ROW_TILED");
-    const bool row_tiled = row_tiled_env ? atoi(row_tiled_env) != 0 : c->n >= 300000;
-    auto blocked = [&](auto &&go) { if (span) go(std::true_type{}); else go(std::false_type{}); };
-    CHK(dispatch_ref_group(c, [&](auto G, auto NZ) {
-        constexpr int g = decltype(G)::value, nz = decltype(NZ)::value;
-        blocked([&](auto BLK) {
-            constexpr bool blk = decltype(BLK)::value;
-            if (row_tiled) {
-                Scope s(c, "k_ref_row_pass");
-                constexpr int tj = 64 / nz;
-                hipLaunchKernelGGL((plsa::ref::k_ref_row_pass_tiled<nz, blk>), dim3(grid_for(c, (nd + tj - 1) / tj, 2)), dim3(128),
-                                   sizeof(float) * 2 * tj * (size_t)(c->kp + 1), c->stream, c->indptr, c->val, nd, order,
-                                   p_base(c), c->U[out_u(c)].as<float>(), d_norm_pdz, c->kp, d0, e0);
-            } else {
-                Scope s(c, "k_ref_row_pass");
-                hipLaunchKernelGGL((plsa::ref::k_ref_row_pass<g, nz, blk>), dim3(grid_for(c, nd, 256 / g)), dim3(256),
-                                   sizeof(float) * (size_t)(256 / g) * c->kp, c->stream, c->indptr, c->val, nd, order,
-                                   p_base(c), c->U[out_u(c)].as<float>(), d_norm_pdz, c->kp, d0, e0);
-            }
-            if (update_v) {
-                Scope s(c, "k_ref_col_pass");
-                hipLaunchKernelGGL((plsa::ref::k_ref_col_pass<g, nz, blk>), dim3(grid_for(c, c->m, 256 / g)), dim3(256), 0, c->stream,
-                                   c->csc.colptr.as<int>(), c->csc.row.as<int>(), c->csc.val.as<float>(), c->csc.pos.as<int>(),
-                                   (int)c->m, p_base(c), d_sw, c->Vacc.as<float>(), c->kp, heavy_min, e0, e1, first);
-            }
-        });
-    }));
-    if (update_v && c->ref_heavy.n > 0) {
-        // the long columns: one workgroup each, the norm_pwz chain's kernel over the column's entries (6.4 ns per entry where a
-        // group's own walk costs ~160: the Zipf head was the pass -- 24.6 ms at the config-3 150 k sample, 157 ms at the whole)
-        Scope s(c, "k_ref_col_heavy");
-        const int kp = c->kp;
-        auto go = [&](auto NZ) {
-            constexpr int nz = decltype(NZ)::value;
-            auto launch = [&](auto SW, auto BLK) {
-                hipLaunchKernelGGL((plsa::ref::k_ref_norm_chain<nz, decltype(SW)::value, true, decltype(BLK)::value>),
-                                   dim3(c->ref_heavy.n), dim3(plsa::ref::CHAIN_THREADS), 0, c->stream, c->csc.row.as<int>(),
-                                   c->csc.val.as<float>(), (i64)0, p_base(c), d_sw, kp, c->Vacc.as<float>(), c->csc.pos.as<int>(),
-                                   c->ref_heavy.cols.as<int>() + 1, c->csc.colptr.as<int>(), e0, e1, first);
-            };
-            blocked([&](auto BLK) { if (d_sw) launch(std::true_type{}, BLK); else launch(std::false_type{}, BLK); });
-        };
-        using std::integral_constant;
-        if (kp <= 64) go(integral_constant<int, 1>{});
-        else if (kp <= 128) go(integral_constant<int, 2>{});
-        else if (kp <= 256) go(integral_constant<int, 4>{});
-        else if (kp <= 512) go(integral_constant<int, 8>{});
-        else go(integral_constant<int, 16>{});
-    }
-    return launch_check(c, "k_ref_row_pass / k_ref_col_pass");
-}
-
-// what the vocabulary half needs before its first launch; *heavy_min: the length from which a column goes to a workgroup of its own
-int prepare_ref_v(plsa_ctx *c, int *heavy_min) {
-    CHK(ensure_csc(c));
-    CHK(ensure_rowidx(c));
-    CHK(ensure_ref_heavy(c));
-    if (c->ref_heavy.n > 0) *heavy_min = c->ref_heavy.min;
-    return ensure(c, c->norm_pwz, sizeof(float) * (size_t)c->kp);
-}
-
-// after the passes and the chain (ev_join): P(w|z) = Vacc / norm_pwz where positive (plsa.py:196-199)
-int run_ref_v_normalise(plsa_ctx *c) {
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    Scope s(c, "k_v_normalise");
-    const i64 total4 = c->m * c->kp / 4;
-    hipLaunchKernelGGL(plsa::k_v_normalise, dim3(grid_for(c, total4, 256)), dim3(256), c->kp * sizeof(float), c->stream,
-                       c->Vacc.as<float>(), c->Vt[out_v(c)].as<float>(), (int)c->m, c->kp, c->norm_pwz.as<float>());
-    return launch_check(c, "k_v_normalise");
-}
-
-// plsa.py:172-204 / 277-310 / 795-816 from the materialised P: U[out], (update_v) Vt[out]; swaps the buffers in.
-// The norm_pwz chain (one workgroup, nnz dependent additions per topic) runs on the second stream beside the document
-// and column passes.
-int run_ref_m_step(plsa_ctx *c, const float *d_sw, bool update_v, float *d_norm_pdz) {
-    if (c->sharded) return fail(c, "the reference arithmetic has no doc-sharded form (norm_pwz is ONE chain over all non-zeros)");
-    const int *order = nullptr;
-    CHK(ensure_roworder(c, &order));               // (here: the sort is enqueued before the fork to the second stream)
-    int heavy_min = INT32_MAX;
-    if (update_v) {
-        CHK(prepare_ref_v(c, &heavy_min));
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-        {
-            LaunchOn on2(c, c->stream2);
-            CHK(run_ref_norm_pwz(c, d_sw));
-        }
-        CHK(launch_check(c, "k_ref_norm_chain"));
-        HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-    }
-    CHK(run_ref_passes(c, d_sw, update_v, d_norm_pdz, heavy_min, order));
-    if (update_v) CHK(run_ref_v_normalise(c));
-    c->cu ^= 1;
-    if (update_v) c->cv ^= 1;
-    return 0;
-}
-
-// The block plan of plsa_set_p_budget for the active matrix: whole documents, in order, as many per block as
-// (block_nnz + 64) * kp * 4 <= budget allows.  (The 64 rows are the slack the tiled E-step stores its last tile into.)
-int ensure_ref_blocks(plsa_ctx *c) {
-    plsa_ctx::RefBlocks &pl = c->ref_blocks;
-    if (pl.valid && pl.budget == c->p_budget && pl.kp == c->kp) return 0;
-    pl.valid = false;                              // (a rebuild that fails leaves no plan behind)
-    const int64_t row_bytes = (int64_t)sizeof(float) * c->kp;
-    const i64 max_rows = c->p_budget / row_bytes - 64;
-    if (max_rows < 1)
-        return fail(c, "plsa_set_p_budget: a budget of %lld bytes holds no row of P(z|w,d): the least usable budget at k = %d is "
-                       "%lld bytes ((1 + 64) * %d * 4)", (long long)c->p_budget, c->k, (long long)(65 * row_bytes), c->kp);
-    pl.doc.assign(1, 0); pl.ent.assign(1, 0);
-    pl.budget = c->p_budget; pl.kp = c->kp; pl.largest = 0;
-    if (c->nnz <= max_rows) {
-        pl.doc.push_back(c->n); pl.ent.push_back(c->nnz);
-        pl.largest = c->nnz;
-    } else {
-        std::vector<int> ip((size_t)c->n + 1);
-        HIPCHK(c, hipMemcpyAsync(ip.data(), c->indptr, sizeof(int) * ip.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        i64 b0 = 0;                                // first entry of the block being filled
-        for (i64 d = 0; d < c->n; ++d) {
-            const i64 len = (i64)ip[d + 1] - ip[d];
-            if (len > max_rows)
-                return fail(c, "plsa_set_p_budget: document %lld has %lld non-zeros, its P(z|w,d) rows alone need %lld bytes "
-                               "((non-zeros + 64) * %d * 4) and the budget is %lld bytes", (long long)d, (long long)len,
-                            (long long)((len + 64) * row_bytes), c->kp, (long long)c->p_budget);
-            if ((i64)ip[d + 1] - b0 > max_rows) {  // document d opens the next block
-                pl.doc.push_back(d); pl.ent.push_back(ip[d]);
-                pl.largest = std::max(pl.largest, (i64)ip[d] - b0);
-                b0 = ip[d];
-            }
-        }
-        pl.doc.push_back(c->n); pl.ent.push_back(c->nnz);
-        pl.largest = std::max(pl.largest, c->nnz - b0);
-    }
-    pl.valid = true;
-    return 0;
-}
-
-// One EM iteration of the reference arithmetic with P(z|w,d) of ONE BLOCK of documents at a time (plsa_set_p_budget): per block
-// the E-step of its entries, its documents' half of the M-step (complete inside the block), and its part of every column's chain
-// and of the norm_pwz chain, each started from what the block before left (Vacc, norm_pwz) -- the additions of run_ref_m_step in
-// the same order.  Streams: the norm_pwz chain of block b runs on the second stream beside the passes of block b, as in the
-// unblocked step; the E-step of block b + 1 overwrites the buffer, so it waits for that chain (ev_join) and, in stream order, for
-// the passes; chain b + 1 follows chain b in the second stream's own order.
-int run_ref_em_blocked(plsa_ctx *c, float thresh, const float *d_sw, bool update_v) {
-    if (c->sharded) return fail(c, "the reference arithmetic has no doc-sharded form (norm_pwz is ONE chain over all non-zeros)");
-    const plsa_ctx::RefBlocks &pl = c->ref_blocks;
-    c->ref_tsum.invalidate(); c->p_state.invalidate();
-    CHK(ensure_p(c, pl.largest));
-    CHK(ensure_rowidx(c));
-    int heavy_min = INT32_MAX;
-    if (update_v) CHK(prepare_ref_v(c, &heavy_min));
-    // (whatever way the loop is left: P holds one block, not the responsibilities of the matrix)
-    struct Forget { plsa_ctx *c; ~Forget() { c->ref_tsum.invalidate(); c->p_state.invalidate(); } } forget{c};
-    const int nb = pl.blocks();
-    for (int b = 0; b < nb; ++b) {
-        const RefSpan span{pl.ent[b], pl.ent[b + 1] - pl.ent[b], (int)pl.doc[b], (int)pl.doc[b + 1], pl.largest, b == 0, b == nb - 1};
-        if (update_v && b > 0) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));     // the chain of block b - 1 has read P
-        c->ref_tsum.invalidate();
-        CHK(run_ref_e_step(c, thresh, &span));
-        if (update_v) {
-            HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-            {
-                LaunchOn on2(c, c->stream2);
-                CHK(run_ref_norm_pwz(c, d_sw, &span));
-            }
-            CHK(launch_check(c, "k_ref_norm_chain"));
-            HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-        }
-        CHK(run_ref_passes(c, d_sw, update_v, nullptr, heavy_min, nullptr, &span));
-    }
-    if (update_v) CHK(run_ref_v_normalise(c));
-    c->cu ^= 1;
-    if (update_v) c->cv ^= 1;
-    return 0;
-}
-
-// plsa.py:372-386 as ONE float32 running sum over the non-zeros (PLSA_REFERENCE_LL)
-int run_ref_loglik(plsa_ctx *c, const float *d_sw, double *out) {
-    if (c->sharded) return fail(c, "the reference arithmetic has no doc-sharded form");
-    CHK(ensure_rowidx(c));
-    CHK(ensure(c, c->ref_terms, sizeof(float) * (size_t)std::max<i64>(c->nnz, 1)));
-    CHK(ensure(c, c->ll_out, sizeof(double)));
-    {
-        Scope s(c, "k_ref_ll_terms");
-        hipLaunchKernelGGL(plsa::ref::k_ref_ll_terms, dim3(grid_for(c, c->nnz, 256)), dim3(256), 0, c->stream,
-                           c->rowidx.ids.as<int>(), c->col, c->val, c->nnz, c->U[c->cu].as<float>(), c->Vt[c->cv].as<float>(),
-                           d_sw, c->kp, c->ref_terms.as<float>());
-    }
-    if (ref_pairs_now(c)) {
-        // the chain of the NEGATED terms from parity pairs (one "topic"); its slow-chunk counts go to their own slots, unread
-        CHK(ensure(c, c->ref_stats, 32));
-        CHK(ensure(c, c->ref_ll_neg, sizeof(float)));
-        unsigned long long *stats = c->ref_stats.as<unsigned long long>();
-        CHK(run_ref_pair_chain(c, plsa::ref::PAIR_NEG_TERMS, c->ref_terms.as<float>(), 1, nullptr, c->ref_ll_neg.as<float>(), stats + 2));
-        hipLaunchKernelGGL(plsa::ref::k_ref_ll_from_walk, dim3(1), dim3(1), 0, c->stream, c->ref_ll_neg.as<float>(), c->ll_out.as<double>());
-    } else {
-        Scope s(c, "k_ref_ll_chain");
-        hipLaunchKernelGGL(plsa::ref::k_ref_ll_chain, dim3(1), dim3(64), 0, c->stream, c->ref_terms.as<float>(), c->nnz,
-                           c->ll_out.as<double>());
-    }
-    CHK(launch_check(c, "k_ref_ll_chain"));
-    HIPCHK(c, hipMemcpyAsync(c->h_ll.get(), c->ll_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *out = c->h_ll[0];
-    return 0;
-}
-
 // the PLSA_* knobs a context reads when it is created (a member context of a batch reads them like its leader)
 void read_knobs(plsa_ctx *c) {
     if (const char *s = getenv("PLSA_OVERLAP")) c->overlap = atoi(s) != 0;
@@ -1961,8 +1482,7 @@ void read_knobs(plsa_ctx *c) {
     if (const char *s = getenv("PLSA_FORCE_WIDE")) c->force_wide = atoi(s) != 0;
     if (const char *s = getenv("PLSA_MT_CHAIN")) c->mt_chain = atoi(s) != 0;
     if (const char *s = getenv("PLSA_SPECULATE")) c->speculate = atoi(s);
-    if (const char *s = getenv("PLSA_REF_CHAIN"))      // norm_pwz of the reference arithmetic: auto (default) | pairs | serial
-        c->ref_chain_mode = !strcmp(s, "pairs") ? 1 : (!strcmp(s, "serial") ? 2 : 0);
+    c->ref_chain_mode = ref_knobs(c, REF_AT_CREATE).chain_mode;      // (plsa_ref.hpp; the other knobs of the reference arithmetic are read per call)
 }
 
 }  // namespace

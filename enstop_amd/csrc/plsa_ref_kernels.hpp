@@ -36,6 +36,8 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "plsa_ref_plan.hpp"
+
 #pragma clang fp contract(off)   // s = x * p is rounded, THEN added (plsa.py:188-194): no fused multiply-add in this file
 
 namespace plsa {
@@ -709,15 +711,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_ref_norm_chain(const int *__r
 // consecutive chunks COMPOSE into one (k_ref_pair_compose: the walk steps through groups and descends into a group only where it has no
 // valid pair), and a chunk's pairs are computed by the adder itself (two proxy sums per binade, k_ref_pair_build).
 // ------------------------------------------------------------------------------------------------
-// Addends per chunk: a kernel argument (a multiple of 64).  A walk step costs ~115 ns whatever the length, a chunk that goes the
-// slow way ~22 ns per addend, and the number of such chunks hardly depends on the corpus (~25 binade crossings per topic, most of them
-// shared by the 64 topics of a group: ~600 chunks per walk at k = 64).  With the groups of PAIR_R chunks the length is 256 everywhere;
-// walking chunks only (PLSA_REF_LEVELS=1) the best length grows with sqrt(nnz) and the host takes 1024 from 48 M non-zeros on
-// (config-3 sample, 15 M: 64 / 128 / 256 -> the four kernels together 39.9 / 27.5 / 24.5 ms in their first form; config 3 whole,
-// 100 M: the walk 49 ms at 256, 24 ms at 1024, 9 ms with the groups).
-constexpr int PAIR_L_SMALL = 256, PAIR_L_LARGE = 1024;
-constexpr long long PAIR_L_LARGE_FROM = 48000000;
-constexpr int PAIR_SC = 8;            // chunks a wave handles back to back (8 consecutive float64 chunk sums per lane: one 64-B line)
+// PAIR_L_*, PAIR_SC, PAIR_R: the chunk constants, shared with the host's arithmetic (plsa_ref_plan.hpp)
 constexpr unsigned PAIR_INVALID = 0x7F000000u;                    // a total no valid pair holds (those stay below 2^25): M + T >= 2^24 by itself
 constexpr unsigned PAIR_NO_BINADE = 0x7FFFu;                      // exps field "no candidate": equals no biased exponent
 constexpr unsigned PAIR_NOOP = 0x80000000u;                       // exps bit: every addend of the chunk is zero (any sum stays what it is)
@@ -926,7 +920,6 @@ __global__ __launch_bounds__(256) void k_ref_pair_build(const int *__restrict__ 
 // parity to a total increment, for as long as every chunk of the group has a valid pair for the SAME binade (a chunk of zeros fits any).
 // The walk then takes one step per group, PAIR_R times fewer, and falls back to the group's chunks where the group has no valid pair
 // (a crossing inside it, chunks that guessed different binades).  Candidates: those of the group's first chunk that has any.
-constexpr int PAIR_R = 16;
 __global__ __launch_bounds__(256) void k_ref_pair_compose(const uint4 *__restrict__ pairs, const unsigned *__restrict__ exps, int kp,
                                                           i64 n_chunks, i64 n_groups, uint4 *__restrict__ pairs2,
                                                           unsigned *__restrict__ exps2) {
