@@ -159,7 +159,11 @@ struct plsa_ctx {
     // packed entry streams of the fused passes (plsa_kernels.hpp: Packed): pk_csr parallel to col / val, pk_csc parallel to
     // csc.row / csc.val.  A stream is used (ok) when its ids fit 24 bits and at most 1/16 of the entries escape.
     bool packed = true;              // PLSA_PACKED=0: the two-array streams everywhere (A/B)
-    struct PackedStream : Derived<PackedStream> { DevBuf buf; bool ok = false; } pk_csr, pk_csc;
+    struct PackedStream : Derived<PackedStream> {
+        DevBuf buf;
+        bool ok = false;
+        int state() const { return !valid ? -1 : (ok ? 1 : 0); }   // -1 not built, 0 the pass runs on the arrays, 1 packed
+    } pk_csr, pk_csc;
     DevBuf pk_count;
     int chunks_per_lane = 2;
     int row_lpn = 1, row_ch = 1;     // lane shape of the DOCUMENT pass (may differ from lpn / ch: see set_shape)
@@ -636,285 +640,11 @@ int grid_for(plsa_ctx *c, i64 work_items, int items_per_block) {
     return plsa::plan::grid_for(work_items, items_per_block, c->grid_cap);
 }
 
-// ---------------------------------------------------------------------------------------------
-// corpus helpers
-// ---------------------------------------------------------------------------------------------
-void set_active_pointers(plsa_ctx *c) {
-    if (c->active_is_base) {
-        c->indptr = c->b_indptr.as<int>(); c->col = c->b_col.as<int>(); c->val = c->b_val.as<float>();
-        c->n = c->bn; c->m = c->bm; c->nnz = c->bnnz;
-    } else {
-        c->indptr = c->a_indptr.as<int>(); c->col = c->a_col.as<int>(); c->val = c->a_val.as<float>();
-    }
-    c->rowidx.invalidate(); c->csc.invalidate(); c->pk_csr.invalidate(); c->pk_csc.invalidate(); c->roworder.invalidate();
-    c->ritems.invalidate(); c->eitems.invalidate(); c->p_state.invalidate(); c->ref_heavy.invalidate(); c->ref_tsum.invalidate();
-    c->ref_blocks.invalidate();
-    c->ref_pairs_off = false;
-}
+}  // namespace
 
-int ensure_rowidx(plsa_ctx *c) {
-    if (c->rowidx.valid) return 0;
-    CHK(ensure(c, c->rowidx.ids, sizeof(int) * (size_t)c->nnz));
-    if (c->n > 0) {
-        Scope s(c, "k_expand_rows");
-        hipLaunchKernelGGL(plsa::k_expand_rows, dim3(grid_for(c, c->n, 4)), dim3(256), 0, c->stream,
-                           c->indptr, (int)c->n, c->rowidx.ids.as<int>());
-    }
-    CHK(launch_check(c, "k_expand_rows"));
-    c->rowidx.valid = true;
-    return 0;
-}
+#include "plsa_structures.hpp"   // what is derived from the active matrix and the lane shape: builders and invalidation rules
 
-// row ids sorted by descending row length (stable), or nullptr when sorting is disabled
-// documents per range of the XCD-contiguous document schedule for the current corpus and lane shape (0: not in use)
-int row_xcd_range(const plsa_ctx *c) {
-    const i64 gpb = 256 / std::max(1, c->row_lpn);
-    if (!c->row_xcd || c->n < 64 * gpb) return 0;
-    return (int)(((c->n + gpb - 1) / gpb + 7) / 8 * gpb);
-}
-
-int ensure_roworder(plsa_ctx *c, const int **out) {
-    *out = nullptr;
-    if (!c->sort_rows) return 0;
-    const int range = row_xcd_range(c);
-    if (!c->roworder.valid || c->roworder.range != range) {
-        c->roworder.range = range;
-        const i64 n = c->n;
-        CHK(ensure(c, c->roworder.ids, sizeof(int) * (size_t)n));
-        CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)n * 2));
-        CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)n));
-        int *len = c->tmp0.as<int>(), *len_sorted = c->tmp0.as<int>() + n, *ids = c->tmp1.as<int>();
-        hipLaunchKernelGGL(plsa::k_row_lengths, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, (int)n, len, ids, range);
-        CHK(launch_check(c, "k_row_lengths"));
-        size_t bytes = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairsDescending(nullptr, bytes, len, len_sorted, ids,
-                                                               c->roworder.ids.as<int>(), (int)n, 0, 32, c->stream));
-        CHK(ensure(c, c->cubtmp, bytes));
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairsDescending(c->cubtmp.p, bytes, len, len_sorted, ids,
-                                                               c->roworder.ids.as<int>(), (int)n, 0, 32, c->stream));
-        c->roworder.valid = true;
-    }
-    *out = c->roworder.ids.as<int>();
-    return 0;
-}
-
-int exclusive_sum_int(plsa_ctx *c, const int *in, int *out, i64 count);
-
-// Decide whether the document pass should run over row items (plsa_launch_plan.hpp: row_items), and build them.
-int ensure_ritems(plsa_ctx *c) {
-    if (c->ritems.valid) return 0;
-    const i64 n = c->n;
-    const plsa::plan::RowItems ri = plsa::plan::row_items(n, c->nnz, c->prop.multiProcessorCount, c->row_lpn, c->ritems_mode,
-                                                          c->rseg_override);
-    c->ritems.use = ri.use;
-    c->ritems.seg = ri.seg;
-    c->ritems.n = 0;
-    if (c->ritems.use) {
-        CHK(ensure(c, c->ritems.first, sizeof(int) * (size_t)(n + 1)));
-        CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)(n + 1)));
-        HIPCHK(c, hipMemsetAsync(c->tmp0.p, 0, sizeof(int) * (size_t)(n + 1), c->stream));
-        hipLaunchKernelGGL(plsa::k_item_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, (int)n, c->ritems.seg, c->tmp0.as<int>());
-        CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->ritems.first.as<int>(), n + 1));
-        int cnt = 0;
-        HIPCHK(c, hipMemcpyAsync(&cnt, c->ritems.first.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ritems.n = cnt;
-        CHK(ensure(c, c->ritems.row, sizeof(int) * (size_t)std::max(cnt, 1)));
-        CHK(ensure(c, c->ritems.start, sizeof(int) * (size_t)std::max(cnt, 1)));
-        hipLaunchKernelGGL(plsa::k_ritem_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, c->ritems.first.as<int>(), (int)n, c->ritems.seg, c->ritems.row.as<int>(),
-                           c->ritems.start.as<int>());
-        CHK(launch_check(c, "k_ritem_fill"));
-    }
-    c->ritems.valid = true;
-    return 0;
-}
-
-// items of the document-owned E-step (its own piece length, independent of the document pass' row items)
-int ensure_eitems(plsa_ctx *c, int eseg) {
-    if (c->eitems.valid && c->eitems.seg == eseg) return 0;
-    const i64 n = c->n;
-    c->eitems.seg = eseg;
-    c->eitems.n = 0;
-    if (eseg > 0) {
-        CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)(n + 1)));
-        CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)(n + 1)));
-        HIPCHK(c, hipMemsetAsync(c->tmp0.p, 0, sizeof(int) * (size_t)(n + 1), c->stream));
-        hipLaunchKernelGGL(plsa::k_item_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, (int)n, eseg, c->tmp0.as<int>());
-        CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->tmp1.as<int>(), n + 1));
-        int cnt = 0;
-        HIPCHK(c, hipMemcpyAsync(&cnt, c->tmp1.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->eitems.n = cnt;
-        CHK(ensure(c, c->eitems.row, sizeof(int) * (size_t)std::max(cnt, 1)));
-        CHK(ensure(c, c->eitems.start, sizeof(int) * (size_t)std::max(cnt, 1)));
-        hipLaunchKernelGGL(plsa::k_ritem_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           c->indptr, c->tmp1.as<int>(), (int)n, eseg, c->eitems.row.as<int>(), c->eitems.start.as<int>());
-        CHK(launch_check(c, "k_ritem_fill"));
-        HIPCHK(c, hipStreamSynchronize(c->stream));      // tmp1 is reused by other structure builds
-    }
-    c->eitems.valid = true;
-    return 0;
-}
-
-int exclusive_sum_int(plsa_ctx *c, const int *in, int *out, i64 count) {
-    size_t bytes = 0;
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)count, c->stream));
-    CHK(ensure(c, c->cubtmp, bytes));
-    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, bytes, in, out, (int)count, c->stream));
-    return 0;
-}
-
-int ensure_csc(plsa_ctx *c) {
-    if (c->csc.valid) return 0;
-    CHK(ensure_rowidx(c));
-    c->csc.seg = plsa::plan::col_item_len(c->nnz, c->prop.multiProcessorCount, c->lpn, c->seg_override);
-    const i64 nnz = c->nnz, m = c->m;
-    CHK(ensure(c, c->csc.colptr, sizeof(int) * (size_t)(m + 1)));
-    CHK(ensure(c, c->csc.row, sizeof(int) * (size_t)nnz));
-    CHK(ensure(c, c->csc.val, sizeof(float) * (size_t)nnz));
-    CHK(ensure(c, c->csc.pos, sizeof(int) * (size_t)nnz));
-    CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)std::max<i64>(nnz, m + 1)));  // counts, then sorted keys
-    CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)nnz));                         // iota
-    // the column pass' packed stream is written by the same gather (documents are its ids)
-    const bool pack = c->packed && nnz > 0 && c->n <= plsa::PACK_MAX_IDS;
-    c->pk_csc.invalidate();
-    c->pk_csc.ok = false;
-    if (pack) {
-        CHK(ensure(c, c->pk_csc.buf, sizeof(unsigned) * (size_t)nnz));
-        CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
-    }
-    // stable sort of entry positions by column: within a column entries stay in document order
-    if (nnz > 0) {
-        hipLaunchKernelGGL(plsa::k_iota, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
-                           c->tmp1.as<int>(), nnz);
-        int bits = 1;
-        while (((i64)1 << bits) < m) ++bits;
-        size_t bytes = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, c->col, c->tmp0.as<int>(),
-                                                     c->tmp1.as<int>(), c->csc.pos.as<int>(), nnz, 0,
-                                                     bits, c->stream));
-        CHK(ensure(c, c->cubtmp, bytes));
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, bytes, c->col, c->tmp0.as<int>(),
-                                                     c->tmp1.as<int>(), c->csc.pos.as<int>(), nnz, 0,
-                                                     bits, c->stream));
-        hipLaunchKernelGGL(plsa::k_colptr_from_sorted, dim3((unsigned)((m + 256) / 256)), dim3(256), 0, c->stream,
-                           c->tmp0.as<int>(), nnz, (int)m, c->csc.colptr.as<int>());
-        hipLaunchKernelGGL(plsa::k_csc_gather, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
-                           c->csc.pos.as<int>(), c->rowidx.ids.as<int>(), c->val, nnz,
-                           c->csc.row.as<int>(), c->csc.val.as<float>(), pack ? c->pk_csc.buf.as<unsigned>() : nullptr,
-                           pack ? c->pk_count.as<unsigned long long>() : nullptr);
-        CHK(launch_check(c, "k_csc_gather"));
-    } else {
-        HIPCHK(c, hipMemsetAsync(c->csc.colptr.p, 0, sizeof(int) * (size_t)(m + 1), c->stream));
-    }
-    // column items
-    CHK(ensure(c, c->csc.item_first, sizeof(int) * (size_t)(m + 1)));
-    HIPCHK(c, hipMemsetAsync(c->tmp0.p, 0, sizeof(int) * (size_t)(m + 1), c->stream));
-    hipLaunchKernelGGL(plsa::k_col_item_counts, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream,
-                       c->csc.colptr.as<int>(), (int)m, c->csc.seg, c->tmp0.as<int>());
-    CHK(exclusive_sum_int(c, c->tmp0.as<int>(), c->csc.item_first.as<int>(), m + 1));
-    int n_items = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_items, c->csc.item_first.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->csc.n_items = n_items;
-    const size_t ni = (size_t)std::max<i64>(n_items, 1);
-    CHK(ensure(c, c->csc.item_col, sizeof(int) * ni));
-    CHK(ensure(c, c->csc.item_start, sizeof(int) * ni));
-    CHK(ensure(c, c->csc.item_end, sizeof(int) * ni));
-    CHK(ensure(c, c->csc.item_order, sizeof(int) * ni));
-    CHK(ensure(c, c->tmp2, sizeof(unsigned long long) * ni * 2));   // sort keys, sorted keys
-    CHK(ensure(c, c->tmp1, sizeof(int) * ni));           // item ids
-    unsigned long long *d_key = c->tmp2.as<unsigned long long>();
-    const int band = plsa::plan::order_band(c->kp, c->order_band);   // band of the visiting order (PLSA_ORDER_BAND documents)
-    // key = band index << len_bits | inverted column length (a column holds at most n entries); first document when band <= 0
-    int len_bits = 1;
-    while (((i64)1 << len_bits) <= c->n) ++len_bits;
-    int key_bits = len_bits;
-    if (band > 0) { i64 n_bands = c->n / band + 1; int bb = 1; while (((i64)1 << bb) < n_bands) ++bb; key_bits = len_bits + bb; }
-    if (n_items > 0)
-        hipLaunchKernelGGL(plsa::k_item_fill, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream,
-                           c->csc.colptr.as<int>(), c->csc.item_first.as<int>(), (int)m, c->csc.seg, c->csc.row.as<int>(),
-                           c->csc.item_col.as<int>(), c->csc.item_start.as<int>(), c->csc.item_end.as<int>(), band, len_bits, d_key,
-                           c->tmp1.as<int>(), n_items);
-    CHK(launch_check(c, "k_item_fill"));
-    if (n_items > 0) {   // visiting order: band-major, Zipf-head words first inside a band (stable)
-        size_t bytes = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_key, d_key + ni,
-                                                     c->tmp1.as<int>(), c->csc.item_order.as<int>(), n_items, 0, key_bits, c->stream));
-        CHK(ensure(c, c->cubtmp, bytes));
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->cubtmp.p, bytes, d_key, d_key + ni,
-                                                     c->tmp1.as<int>(), c->csc.item_order.as<int>(), n_items, 0, key_bits, c->stream));
-    }
-    // visiting-order records (one 16-byte load per item instead of an index chain)
-    CHK(ensure(c, c->csc.item_rec, sizeof(int4) * ni));
-    if (n_items > 0) {
-        hipLaunchKernelGGL(plsa::k_item_records, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, c->stream,
-                           c->use_item_order ? c->csc.item_order.as<int>() : nullptr, c->csc.item_col.as<int>(),
-                           c->csc.item_start.as<int>(), c->csc.item_end.as<int>(), (i64)n_items, c->csc.item_rec.as<int4>());
-        CHK(launch_check(c, "k_item_records"));
-    }
-    c->csc.balanced = false;
-    // columns whose item count makes a single group's serial reduction a tail (Zipf head words)
-    CHK(ensure(c, c->csc.heavy_cols, sizeof(int) * (size_t)(m + 1)));
-    HIPCHK(c, hipMemsetAsync(c->csc.heavy_cols.as<int>() + m, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(plsa::k_heavy_list, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream,
-                       c->csc.item_first.as<int>(), (int)m, c->heavy_items, c->csc.heavy_cols.as<int>(),
-                       c->csc.heavy_cols.as<int>() + m);
-    CHK(launch_check(c, "k_heavy_list"));
-    HIPCHK(c, hipMemcpyAsync(&c->csc.n_heavy, c->csc.heavy_cols.as<int>() + m, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    unsigned long long escaped = 0;
-    if (pack) HIPCHK(c, hipMemcpyAsync(&escaped, c->pk_count.p, sizeof escaped, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->csc.valid = true;
-    c->pk_csc.valid = c->packed;
-    c->pk_csc.ok = pack && escaped * 16 <= (unsigned long long)nnz;
-    if (!c->pk_csc.ok) c->pk_csc.buf.release();
-    return 0;
-}
-
-// Packed entry stream of one pass (plsa_kernels.hpp: Packed) from its (id, count) arrays; *ok: the stream is eligible
-// (ids below 2^24 -- `id_range` of them -- and at most 1/16 of the entries escaped to the float array).  An ineligible
-// stream is not kept: its pass runs on the two arrays.
-int build_packed(plsa_ctx *c, DevBuf &out, const int *ids, const float *vals, i64 id_range, bool *ok) {
-    *ok = false;
-    const i64 nnz = c->nnz;
-    if (nnz <= 0 || id_range > plsa::PACK_MAX_IDS) { out.release(); return 0; }
-    CHK(ensure(c, out, sizeof(unsigned) * (size_t)nnz));
-    CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(plsa::k_pack_entries, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
-                       ids, vals, nnz, out.as<unsigned>(), c->pk_count.as<unsigned long long>());
-    CHK(launch_check(c, "k_pack_entries"));
-    unsigned long long escaped = 0;
-    HIPCHK(c, hipMemcpyAsync(&escaped, c->pk_count.p, sizeof escaped, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *ok = escaped * 16 <= (unsigned long long)nnz;
-    if (!*ok) out.release();
-    return 0;
-}
-
-// the document pass' packed stream: built on the first fused pass after an upload / bootstrap / generate
-int ensure_packed_csr(plsa_ctx *c) {
-    if (!c->packed || c->pk_csr.valid) return 0;
-    CHK(build_packed(c, c->pk_csr.buf, c->col, c->val, c->m, &c->pk_csr.ok));
-    c->pk_csr.valid = true;
-    return 0;
-}
-
-// the column pass' packed stream: written by ensure_csc; rebuilt from the CSC arrays after plsa_release_scratch
-int ensure_packed_csc(plsa_ctx *c) {
-    CHK(ensure_csc(c));
-    if (!c->packed || c->pk_csc.valid) return 0;
-    CHK(build_packed(c, c->pk_csc.buf, c->csc.row.as<int>(), c->csc.val.as<float>(), c->n, &c->pk_csc.ok));
-    c->pk_csc.valid = true;
-    return 0;
-}
+namespace {
 
 int upload_sw(plsa_ctx *c, const float *sw, const float **d_sw) {
     *d_sw = nullptr;
@@ -935,26 +665,6 @@ int upload_sw(plsa_ctx *c, const float *sw, const float **d_sw) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *d_sw = c->sw.as<float>();
     return 0;
-}
-
-// lane decomposition of a k-vector (see plsa_kernels.hpp) + invalidation of the structures that depend on it
-void set_shape(plsa_ctx *c, int k) {
-    const plsa::plan::LaneShape sh = plsa::plan::lane_shape(k, c->chunks_per_lane, c->row_shape_8x2);
-    const int prev_lpn = c->struct_lpn, prev_row_lpn = c->struct_row_lpn, lpn = sh.lpn;
-    c->k = k; c->kp = sh.kp;
-    c->lpn = sh.lpn; c->ch = sh.ch;
-    c->row_lpn = sh.row_lpn; c->row_ch = sh.row_ch;
-    // the row-item decision and length follow the DOCUMENT pass' lane count (ensure_ritems), which changes between
-    // kp = 60 and kp = 64 while lpn stays 16: watched on its own
-    if (c->row_lpn != prev_row_lpn) {
-        c->ritems.invalidate();
-        c->struct_row_lpn = c->row_lpn;
-    }
-    if (lpn != prev_lpn) {        // column item lengths depend on the lane shape
-        c->eitems.invalidate();
-        if (!c->seg_override) c->csc.invalidate();
-        c->struct_lpn = lpn;
-    }
 }
 
 int need_factors(plsa_ctx *c) {
@@ -1026,10 +736,7 @@ int run_e_step(plsa_ctx *c, float thresh) {
     if (c->ref_sums) return run_ref_e_step(c, thresh);
     bool e_rows = c->e_rows < 0 ? (double)c->nnz * c->kp >= 1e8 : c->e_rows != 0;
     if (e_rows) {
-        // piece length: measured optimum 64 entries at k = 64 (48: 4.86, 64: 4.61, 80: 5.03, whole documents:
-        // 5.36 ms at config 3; config 5, k = 128: flat within 1 % from 32 to 128), 8 entries at k = 32
-        // (0.224 against 0.234-0.238 ms for 16-40 and 0.316 ms for whole documents at config 2)
-        const int eseg = c->eseg_override >= 0 ? c->eseg_override : (c->lpn >= 16 ? 64 : (c->lpn == 8 ? 8 : 16));
+        const int eseg = plsa::plan::e_item_len(c->lpn, c->eseg_override);
         CHK(ensure_eitems(c, eseg));
         const bool items = eseg > 0 && c->eitems.n > 0;
         const int grid = grid_for(c, items ? c->eitems.n : c->n, 256 / c->lpn);
@@ -1153,89 +860,6 @@ int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, floa
     }));
     CHK(launch_check(c, "k_row_pass"));
     if (ll_blocks) *ll_blocks = r.plan.grid;
-    return 0;
-}
-
-// chunk boundaries of the column pass from the current fractions
-void balance_set_lo(plsa_ctx *c, int n_chunks) {
-    plsa::plan::balance_lo(c->bal_frac, n_chunks, c->bal_lo);
-    c->bal_chunks = n_chunks;
-}
-
-// Measured XCD boundaries of the column pass (see k_col_pass).  `launch(timed)` enqueues one column pass on c->ls.
-// Equal stretches first (or the fractions measured for the previous structure on this context: a bootstrap
-// resample of the same corpus has the same profile and gets one measurement + one correction), then one untimed and up
-// to eight timed launches: every workgroup records its end time, an XCD's time is its last workgroup's, and every stretch is
-// resized by (mean time / own time), damped -- until the eight finish within 2 % of each other.  Results never
-// depend on the boundaries (partials are per item, norm_pwz rows per chunk), only the speed does.
-template <class Launch>
-int ensure_balance(plsa_ctx *c, int n_chunks, bool split, Launch &&launch) {
-    if (c->csc.balanced && c->bal_chunks == n_chunks) return 0;
-    CHK(ensure(c, c->csc.xcd_lo, sizeof(int) * 16));
-    const bool warm = c->bal_have_frac;
-    if (!warm) for (int x = 0; x <= 8; ++x) c->bal_frac[x] = x / 8.0;
-    balance_set_lo(c, n_chunks);
-    HIPCHK(c, hipMemcpyAsync(c->csc.xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
-    c->bal_launches = 0;
-    // auto: corpora from ~1e8 cells per iteration (config 2: 4279 -> 4540 iterations/s; the tuning launches of a
-    // 20NG-sized corpus would cost a bootstrap member more than they return)
-    // PLSA_SMALL_GRID caps the launch below plan::col_grid(): workgroup b would no longer be chunk-stretch b's only visitor
-    // and the start stamp would land in a slot read as an end time -- that experiment knob runs on equal stretches
-    const bool small_grid_active = c->small_grid > 0 && (double)c->nnz * c->kp < c->overlap_full_limit;
-    const bool tune = split && n_chunks >= 64 && !small_grid_active &&
-                      (c->balance > 0 || (c->balance < 0 && (double)c->nnz * c->kp >= 1e8));
-    if (tune) {
-        const size_t cap = (size_t)8 * (size_t)n_chunks + 16;      // any boundaries: at most 8 x n_chunks workgroups
-        CHK(ensure(c, c->t_end, sizeof(unsigned long long) * cap));
-        std::vector<unsigned long long> te;
-        const int max_launches = warm ? 1 : 8;     // a resample of the same corpus: one measurement, one correction
-        if (!warm) CHK(launch(false));             // first structure on this context: clocks and caches warm before timing
-        double best_spread = 1e300, best_frac[9];
-        for (int x = 0; x <= 8; ++x) best_frac[x] = c->bal_frac[x];
-        for (int it = 0; it < max_launches; ++it) {
-            const int grid = plsa::plan::col_grid(c->bal_lo, n_chunks, split);
-            te.assign((size_t)grid + 1, 0);
-            HIPCHK(c, hipMemsetAsync(c->t_end.p, 0, sizeof(unsigned long long) * ((size_t)grid + 1), c->ls));
-            CHK(launch(true));
-            HIPCHK(c, hipMemcpyAsync(te.data(), c->t_end.p, sizeof(unsigned long long) * ((size_t)grid + 1),
-                                     hipMemcpyDeviceToHost, c->ls));
-            HIPCHK(c, hipStreamSynchronize(c->ls));
-            c->bal_launches++;
-            unsigned long long t0 = ~0ull, last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int b = 0; b <= grid; ++b) if (te[b]) t0 = std::min(t0, te[b]);
-            for (int b = 0; b < grid; ++b) last[b & 7] = std::max(last[b & 7], te[b]);
-            double T[8], mean = 0.0, lo_t = 1e300, hi_t = 0.0;
-            for (int x = 0; x < 8; ++x) {
-                T[x] = std::max(1.0, (double)(last[x] - t0) / 100.0);       // us (100 MHz wall clock)
-                c->bal_end_us[x] = T[x];
-                mean += T[x] / 8.0; lo_t = std::min(lo_t, T[x]); hi_t = std::max(hi_t, T[x]);
-            }
-            const double spread = (hi_t - lo_t) / mean;
-            if (spread < best_spread) {            // remember the best boundaries seen (a noisy launch must not have the last word)
-                best_spread = spread;
-                for (int x = 0; x <= 8; ++x) best_frac[x] = c->bal_frac[x];
-            }
-            if (spread <= 0.02) break;
-            if (it == max_launches - 1 && !warm) {   // out of launches: keep the best measured boundaries
-                for (int x = 0; x <= 8; ++x) c->bal_frac[x] = best_frac[x];
-                balance_set_lo(c, n_chunks);
-                HIPCHK(c, hipMemcpyAsync(c->csc.xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
-                break;
-            }
-            double size[8], tot = 0.0;
-            for (int x = 0; x < 8; ++x) {
-                size[x] = std::max(1e-6, (c->bal_frac[x + 1] - c->bal_frac[x]) * (1.0 + 0.8 * (mean / T[x] - 1.0)));
-                tot += size[x];
-            }
-            double acc = 0.0;
-            for (int x = 0; x < 8; ++x) { acc += size[x]; c->bal_frac[x + 1] = acc / tot; }
-            c->bal_frac[8] = 1.0;
-            balance_set_lo(c, n_chunks);
-            HIPCHK(c, hipMemcpyAsync(c->csc.xcd_lo.p, c->bal_lo, sizeof(int) * 9, hipMemcpyHostToDevice, c->ls));
-        }
-        c->bal_have_frac = true;
-    }
-    c->csc.balanced = true;
     return 0;
 }
 
@@ -1630,10 +1254,10 @@ int plsa_bootstrap(plsa_ctx *c, const int64_t *idx, int64_t n_out) {
     {
         // int lengths summed into int64 pointers (a resample may exceed the base nnz)
         auto in64 = hipcub::TransformInputIterator<i64, hipcub::CastOp<i64>, int *>(d_len, hipcub::CastOp<i64>());
-        size_t bytes = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in64, d_ptr, (int)(n_out + 1), c->stream));
-        CHK(ensure(c, c->cubtmp, bytes));
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, bytes, in64, d_ptr, (int)(n_out + 1), c->stream));
+        auto scan = [&](void *tmp, size_t &bytes) {
+            return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in64, d_ptr, (int)(n_out + 1), c->stream);
+        };
+        CHK(cub_two_phase(c, "hipcub::DeviceScan::ExclusiveSum", scan));
     }
     i64 total = 0;
     int bad = 0;
@@ -2275,8 +1899,8 @@ int plsa_schedule_info(plsa_ctx *c, int32_t *xcd_lo, double *xcd_end_us, int32_t
 }
 
 int plsa_packed_info(plsa_ctx *c, int32_t *csr, int32_t *csc) {
-    if (csr) *csr = !c->packed ? 0 : (c->pk_csr.valid ? (c->pk_csr.ok ? 1 : 0) : -1);
-    if (csc) *csc = !c->packed ? 0 : (c->csc.valid && c->pk_csc.valid ? (c->pk_csc.ok ? 1 : 0) : -1);
+    if (csr) *csr = c->packed ? c->pk_csr.state() : 0;       // (PLSA_PACKED=0: the arrays, built or not)
+    if (csc) *csc = c->packed ? c->pk_csc.state() : 0;
     return 0;
 }
 
@@ -2762,18 +2386,17 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
     double mean_tokens = 1.4 * (double)nnz_target / (double)n;
     i64 T = 0;
     int nnz = 0;
-    int dbits = 1;
-    while (((i64)1 << dbits) < n) ++dbits;
+    const int dbits = plsa::plan::sort_bits(n);
     for (int round = 0; round < 8; ++round) {
         const double mu = std::log(mean_tokens) - 0.5 * sigma * sigma;
         hipLaunchKernelGGL(plsa::k_synth_doc_tokens, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream,
                            (int)n, mu, sigma, (int)std::min<i64>(m * 4, 1 << 20), seed, d_tok.as<int>());
         {
             auto in64 = hipcub::TransformInputIterator<i64, hipcub::CastOp<i64>, int *>(d_tok.as<int>(), hipcub::CastOp<i64>());
-            size_t bytes = 0;
-            SYNHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in64, d_ptr.as<i64>(), (int)(n + 1), c->stream));
-            CHK(ensure(c, c->cubtmp, bytes));
-            SYNHIP(hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, bytes, in64, d_ptr.as<i64>(), (int)(n + 1), c->stream));
+            auto scan = [&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in64, d_ptr.as<i64>(), (int)(n + 1), c->stream);
+            };
+            CHK(cub_two_phase(c, "hipcub::DeviceScan::ExclusiveSum", scan));
         }
         SYNHIP(hipMemcpyAsync(&T, d_ptr.as<i64>() + n, sizeof(i64), hipMemcpyDeviceToHost, c->stream));
         SYNHIP(hipStreamSynchronize(c->stream));
@@ -2790,20 +2413,19 @@ static int generate_synthetic_impl(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
             hipLaunchKernelGGL(plsa::k_synth_draw, dim3(grid_for(c, n, 4)), dim3(256), 0, c->stream, (int)n, (int)m,
                                d_ptr.as<i64>(), d_cdf.as<double>(), a, b, seed, d_keys.as<unsigned long long>());
         {
-            size_t bytes = 0;
-            SYNHIP(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, d_keys.as<unsigned long long>(),
-                                                     d_keys2.as<unsigned long long>(), T, 0, 32 + dbits, c->stream));
-            CHK(ensure(c, c->cubtmp, bytes));
-            SYNHIP(hipcub::DeviceRadixSort::SortKeys(c->cubtmp.p, bytes, d_keys.as<unsigned long long>(),
-                                                     d_keys2.as<unsigned long long>(), T, 0, 32 + dbits, c->stream));
+            auto sort = [&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, d_keys.as<unsigned long long>(),
+                                                         d_keys2.as<unsigned long long>(), T, 0, 32 + dbits, c->stream);
+            };
+            CHK(cub_two_phase(c, "hipcub::DeviceRadixSort::SortKeys", sort));
         }
         hipLaunchKernelGGL(plsa::k_synth_heads, dim3(grid_for(c, T, 256)), dim3(256), 0, c->stream,
                            d_keys2.as<unsigned long long>(), T, d_flag.as<int>());
         {
-            size_t bytes = 0;
-            SYNHIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_flag.as<int>(), d_pos.as<int>(), (int)T, c->stream));
-            CHK(ensure(c, c->cubtmp, bytes));
-            SYNHIP(hipcub::DeviceScan::ExclusiveSum(c->cubtmp.p, bytes, d_flag.as<int>(), d_pos.as<int>(), (int)T, c->stream));
+            auto scan = [&](void *tmp, size_t &bytes) {
+                return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_flag.as<int>(), d_pos.as<int>(), (int)T, c->stream);
+            };
+            CHK(cub_two_phase(c, "hipcub::DeviceScan::ExclusiveSum", scan));
         }
         int last_pos = 0, last_flag = 0;
         SYNHIP(hipMemcpyAsync(&last_pos, d_pos.as<int>() + (T - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));

@@ -699,7 +699,7 @@ __device__ __forceinline__ void col_batch(int s0, int d_l, float x_l, int p_l, i
 // one chunk = one trip of a workgroup, one item per group.  Workgroup b runs on XCD b % 8 (observed dispatch rule; a
 // different placement only costs speed) and XCD x walks the chunks [xcd_lo[x], xcd_lo[x+1]) -- a contiguous stretch
 // of the list, so that all workgroups sharing an L2 gather from the same band of U rows.  The boundaries are
-// MEASURED (plsa_hip.hip::ensure_balance: the TIMED instantiation records every workgroup's end time and the
+// MEASURED (plsa_structures.hpp: ensure_balance: the TIMED instantiation records every workgroup's end time and the
 // stretches are resized until the eight XCDs finish together): equal stretches left the XCD holding the
 // rare-word items -- they sort to the front of the list and all their gathers miss -- 35 % behind the fastest one
 // (round 3: 2.35 -> 2.06 ms at config 3 with 256-entry items, 1.93 ms with 128).
@@ -1329,17 +1329,13 @@ __global__ __launch_bounds__(256) void k_csc_gather(const int *__restrict__ pos,
     }
     if (packed) add_escapes(esc, n_esc);
 }
+// items per row of a CSR / column of a CSC: a row is cut into pieces of <= seg entries (documents: k_ritem_fill; columns: k_item_fill)
 __global__ void k_item_counts(const int *__restrict__ colptr, int m, int seg, int *__restrict__ cnt) {
     const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (c < m) cnt[c] = (colptr[c + 1] - colptr[c] + seg - 1) / seg;
 }
-// item arrays + the first document of every item (sort key of the doc-band-major visiting order)
-// Column items: a column is cut into chunks of <= seg entries (explicit [item_start, item_end) bounds).
-__global__ void k_col_item_counts(const int *__restrict__ colptr, int m, int seg, int *__restrict__ cnt) {
-    const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < m) cnt[c] = (colptr[c + 1] - colptr[c] + seg - 1) / seg;
-}
 
+// Column items: item arrays (explicit [item_start, item_end) bounds) + the sort key of the doc-band-major visiting order.
 // Sort key of an item for the visiting order: (band of its first document, column length descending).  Band-major
 // keeps the workgroups of an XCD inside one band of P(z|d) rows; inside a band the Zipf-head words go first (they
 // touch every row of the band and pull it into the L2) and a chunk's 16 items are of one kind -- a chunk whose

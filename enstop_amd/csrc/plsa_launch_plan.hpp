@@ -1,8 +1,9 @@
 // plsa_launch_plan.hpp -- the arithmetic behind how a fused pass is launched, free of HIP: lane shape from k, item lengths,
-// grids, the two-stage switch of the norm, the XCD stretches, the wide-table rule.  Plain integers in, plain values out: no
-// context, no device memory, no environment.  plsa_hip.hip's prepare_row_pass / prepare_col_pass turn these into the
-// structures, scratch and grids of one pass (the fit, the batched members and the NMF all launch from those);
-// tests/launch_plan_host.cpp runs every function on a CPU.
+// grids, the two-stage switch of the norm, the XCD stretches and their balance controller, the wide-table rule, and what the
+// structure builders compute on the host: sort bits, the E-step's piece length, the packing rule.  Plain values in, plain
+// values out: no context, no device memory, no environment.  plsa_hip.hip's prepare_row_pass / prepare_col_pass turn these
+// into the structures (built by plsa_structures.hpp), scratch and grids of one pass (the fit, the batched members and the
+// NMF all launch from those); tests/launch_plan_host.cpp runs every function on a CPU.
 #pragma once
 
 #include <algorithm>
@@ -87,6 +88,39 @@ inline int order_band(int kp, int order_band_knob) {
     return order_band_knob >= 0 ? order_band_knob : std::max(64, band_bytes / (kp > 0 ? kp * 4 : 256));
 }
 
+// Bits a radix sort has to look at for keys 0 .. count - 1: the smallest b >= 1 with 2^b >= count.  One too few sorts wrongly,
+// and silently.
+inline int sort_bits(int64_t count) {
+    int bits = 1;
+    while (((int64_t)1 << bits) < count) ++bits;
+    return bits;
+}
+
+// Key of the column items' visiting order (k_item_fill): band index << len_bits | inverted column length.  A column holds at
+// most n entries, so len_bits are the bits of 0 .. n; above them the bits of the n / band + 1 bands (band <= 0: the key is
+// the item's first document, which fits len_bits too).  len_bits goes to k_item_fill, key_bits to the sort.
+struct OrderKey { int len_bits, key_bits; };
+inline OrderKey order_key(int64_t n, int band) {
+    OrderKey k;
+    k.len_bits = sort_bits(n + 1);
+    k.key_bits = k.len_bits + (band > 0 ? sort_bits(n / band + 1) : 0);
+    return k;
+}
+
+// Entries per piece of the document-owned E-step (eseg_override >= 0: that many, 0 = whole documents).  Measured optimum 64
+// entries at k = 64 (48: 4.86, 64: 4.61, 80: 5.03, whole documents: 5.36 ms at config 3; config 5, k = 128: flat within 1 %
+// from 32 to 128), 8 entries at k = 32 (0.224 against 0.234-0.238 ms for 16-40 and 0.316 ms for whole documents at config 2)
+inline int e_item_len(int lpn, int eseg_override) {
+    return eseg_override >= 0 ? eseg_override : (lpn >= 16 ? 64 : (lpn == 8 ? 8 : 16));
+}
+
+// A pass runs on its packed entry stream (plsa_kernels.hpp: Packed) when there are entries, its `id_range` ids fit the word's
+// 24 bits and at most 1/16 of the entries escaped to the float array.  With escaped = 0: whether packing is worth trying.
+constexpr int64_t PACK_ID_RANGE = (int64_t)1 << 24;
+inline bool packed_ok(int64_t nnz, int64_t id_range, uint64_t escaped) {
+    return nnz > 0 && id_range <= PACK_ID_RANGE && escaped * 16 <= (uint64_t)nnz;
+}
+
 inline int grid_for(int64_t work, int per_block, int cap) {
     int64_t need = (work + per_block - 1) / per_block;
     if (need < 1) need = 1;
@@ -149,6 +183,40 @@ inline int col_grid(const int lo[9], int n_chunks, bool split) {
         g = 8 * (int64_t)longest;
     }
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, (int64_t)1 << 22));
+}
+
+// The measured balance of the XCD stretches (plsa_structures.hpp: ensure_balance).  A timed launch of `grid` workgroups leaves
+// grid + 1 stamps of the 100 MHz wall clock: workgroup b's end in stamps[b], the start in stamps[grid].  Workgroup b runs on
+// XCD b % 8, an XCD's time is its last workgroup's end after the earliest stamp of the launch (a zero is a stamp never
+// written: not a start), in us, at least 1; spread = (slowest - fastest) / mean.
+struct XcdTimes { double us[8], spread; };
+inline XcdTimes xcd_times(const unsigned long long *stamps, int grid) {
+    unsigned long long t0 = ~0ull, last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int b = 0; b <= grid; ++b) if (stamps[b]) t0 = std::min(t0, stamps[b]);
+    for (int b = 0; b < grid; ++b) last[b & 7] = std::max(last[b & 7], stamps[b]);
+    XcdTimes t;
+    double mean = 0.0, lo_t = 1e300, hi_t = 0.0;
+    for (int x = 0; x < 8; ++x) {
+        t.us[x] = std::max(1.0, (double)(last[x] - t0) / 100.0);
+        mean += t.us[x] / 8.0; lo_t = std::min(lo_t, t.us[x]); hi_t = std::max(hi_t, t.us[x]);
+    }
+    t.spread = (hi_t - lo_t) / mean;
+    return t;
+}
+
+// The next fractions from the current ones and the XCD times they gave: every stretch resized by (mean time / own time),
+// damped by 0.8, never below 1e-6 of the list, and the eight renormalised to the whole list.  next may be frac itself.
+inline void balance_step(const double frac[9], const double us[8], double next[9]) {
+    double mean = 0.0, size[8], tot = 0.0;
+    for (int x = 0; x < 8; ++x) mean += us[x] / 8.0;
+    for (int x = 0; x < 8; ++x) {
+        size[x] = std::max(1e-6, (frac[x + 1] - frac[x]) * (1.0 + 0.8 * (mean / us[x] - 1.0)));
+        tot += size[x];
+    }
+    double acc = 0.0;
+    next[0] = frac[0];
+    for (int x = 0; x < 8; ++x) { acc += size[x]; next[x + 1] = acc / tot; }
+    next[8] = 1.0;
 }
 
 // The two fused passes gather rows of a factor table by index with 32-bit byte offsets (plsa_kernels.hpp: gather_row).

@@ -12,6 +12,12 @@
 //     xcd_split knob n_chunks n kp                          -> 0 | 1
 //     balance n_chunks frac[0..9) (hex floats)              -> lo[0..9) split_grid unsplit_grid
 //     table_is_wide rows kp force                           -> 0 | 1
+//     sort_bits count                                       -> bits
+//     order_key n band                                      -> len_bits key_bits
+//     e_item_len lpn override                               -> entries per piece
+//     packed_ok nnz id_range escaped                        -> 0 | 1
+//     xcd_times grid stamps[0..grid]                        -> us[0..8) spread (hex floats)
+//     balance_step frac[0..9) us[0..8) (hex floats)         -> next frac[0..9) (hex floats)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,6 +77,37 @@ int main() {
             plan::balance_lo(frac.get(), (int)a, lo.get());
             for (int x = 0; x < 9; ++x) std::printf("%d ", lo[x]);
             std::printf("%d %d\n", plan::col_grid(lo.get(), (int)a, true), plan::col_grid(lo.get(), (int)a, false));
+        } else if (!std::strcmp(name, "sort_bits")) {
+            args(1);
+            std::printf("%d\n", plan::sort_bits(a));
+        } else if (!std::strcmp(name, "order_key")) {
+            args(2);
+            const plan::OrderKey k = plan::order_key(a, (int)b);
+            std::printf("%d %d\n", k.len_bits, k.key_bits);
+        } else if (!std::strcmp(name, "e_item_len")) {
+            args(2);
+            std::printf("%d\n", plan::e_item_len((int)a, (int)b));
+        } else if (!std::strcmp(name, "packed_ok")) {
+            args(3);
+            std::printf("%d\n", plan::packed_ok(a, b, (uint64_t)c) ? 1 : 0);
+        } else if (!std::strcmp(name, "xcd_times")) {
+            args(1);
+            // exactly grid + 1 stamps, from the heap
+            std::unique_ptr<unsigned long long[]> stamps(new unsigned long long[(size_t)a + 1]);
+            for (long long i = 0; i <= a; ++i)
+                if (std::scanf("%llu", &stamps[(size_t)i]) != 1) { std::fprintf(stderr, "bad case: xcd_times\n"); std::abort(); }
+            const plan::XcdTimes t = plan::xcd_times(stamps.get(), (int)a);
+            for (int x = 0; x < 8; ++x) std::printf("%a ", t.us[x]);
+            std::printf("%a\n", t.spread);
+        } else if (!std::strcmp(name, "balance_step")) {
+            std::unique_ptr<double[]> frac(new double[9]), us(new double[8]), next(new double[9]);
+            for (int x = 0; x < 17; ++x) {
+                char text[64];
+                if (std::scanf("%63s", text) != 1) { std::fprintf(stderr, "bad case: balance_step\n"); std::abort(); }
+                (x < 9 ? frac[x] : us[x - 9]) = std::strtod(text, nullptr);
+            }
+            plan::balance_step(frac.get(), us.get(), next.get());
+            for (int x = 0; x < 9; ++x) std::printf("%a%c", next[x], x < 8 ? ' ' : '\n');
         } else if (!std::strcmp(name, "table_is_wide")) {
             args(3);
             std::printf("%d\n", plan::table_is_wide(a, (int)b, c != 0) ? 1 : 0);

@@ -15,8 +15,9 @@ and no kernel reads scratch it did not write.  Two checks of that:
   bit for bit with the same operation on a fresh Engine that holds only its corpus, topic count and factors.  REQUIRED
   is the list of transitions the sequence must contain (test_walk_reaches_every_transition, CPU); the fresh result of
   `step` for every (corpus, k) is held to step64 with the pass matrix's bounds.
-* directed cases, one test each: row items across the 16 x 1 / 8 x 2 document-pass shapes at k = 60 / 64, shrinking and
-  growing buffers, the process-wide engine behind the estimators, status-code failures.
+* directed cases, one test each: row items across the 16 x 1 / 8 x 2 document-pass shapes at k = 60 / 64, the structure
+  builders under forced item lengths, shrinking and growing buffers, the process-wide engine behind the estimators,
+  status-code failures.
 
 Corpora (small: 60 002 non-zeros at most).  A: the pass matrix's corpus (matrix_corpus(6): empty documents, a 300-entry
 document, a word in every document, stored zeros, escaped counts) with the factors matrix_corpus(k) seeds for each k.
@@ -780,6 +781,121 @@ def test_row_items_follow_the_document_pass_shape(amd):
             got, shape = _two_iterations(amd, eng, *factors[second])
             assert shape[:2] == ((16, 1) if second == 60 else (8, 2)), shape
             assert_same(got, fresh[second], "k=%d after k=%d on the same upload" % (second, first))
+
+
+def _builder_corpus():
+    """300 x 200: word 0 in every document (300 entries: 38 column items of 8, a heavy column), document 7 with 150 entries
+    (10 row items of 16), the others about 10 entries"""
+    rs = np.random.RandomState(31)
+    mask = rs.rand(300, 200) < 0.05
+    mask[:, 0] = True
+    mask[7, :] = False
+    mask[7, rs.choice(200, 150, replace=False)] = True
+    mask[7, 0] = True
+    r, c = np.nonzero(mask)
+    X = sp.csr_matrix((rs.randint(1, 8, size=r.shape[0]).astype(np.float32), (r, c)), shape=mask.shape)
+    assert X.getnnz(axis=0)[0] == 300 and 150 <= X.getnnz(axis=1)[7] <= 151
+    return X
+
+
+BUILDER_KNOBS = dict(PLSA_ROW_ITEMS="1", PLSA_ROW_SEG="16", PLSA_COL_SEG="8")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ("default", "reference", "e_rows"))
+def test_structure_builders_on_a_reused_context(amd, monkeypatch, variant):
+    """Row items, E-step items, the CSC copy, the packed streams and the XCD stretches come from the builders of
+    csrc/plsa_structures.hpp, the only code that tells a fresh context from one whose structures were built for something
+    else.  One context, the smallest corpus on which each builder has more than one path (forced row items of 16 entries,
+    column items of 8: several items per long row and column, a heavy column), four steps:
+
+    1. a fit at k = 8;
+    2. a fit at k = 64 on the same upload: another lane shape, so the row items and the E-step items are rebuilt.  The CSC
+       copy is NOT: PLSA_COL_SEG fixes the column item length, and set_shape then keeps the copy (item_entries and n_items
+       must stay what they were).  Steps 3 and 4 are what rebuilds the column side here;
+    3. release_scratch and k = 8 again: the packed streams are gone and come back from the CSC arrays;
+    4. a bootstrap resample and a fit, then the base corpus and k = 8 a third time: every structure is rebuilt, twice.
+
+    Every fit and what packed_info / pass_info / balance_info say after it equal those of a context created for that fit
+    alone.  In the default arithmetic; in the reference arithmetic; and in the default arithmetic with PLSA_E_ROWS=1, where
+    every step also runs the E-step, over its own items, on the fitted factors and compares P(z|w,d).
+    The walk above meets the same transitions, but with the knobs' defaults, under which no corpus of it has row items of
+    more than one length, column items of a forced length or E-step items at all.
+
+    One comparison is not with the fresh context.  plsa_release_scratch frees both packed streams, and only a fused pass
+    writes the column stream again (ensure_packed_csc): nothing else reads it.  A fit in the reference arithmetic has no fused
+    pass, so after step 3 its context must say csc: None (include/plsa_hip_diag.h: -1, not built yet), where a fresh one says
+    'packed' only because k_csc_gather wrote the stream while it built the copy.  The reused context is held to exactly that:
+    None for both streams, in the reference arithmetic, after release_scratch; equal to the fresh context everywhere else."""
+    for name, value in BUILDER_KNOBS.items():
+        monkeypatch.setenv(name, value)
+    if variant == "e_rows":
+        monkeypatch.setenv("PLSA_E_ROWS", "1")
+    flags = 0 if variant == "reference" else amd.PLSA_FUSED
+    X = _builder_corpus()
+    n, m = X.shape
+    idx = np.random.RandomState(32).randint(0, n, size=n).astype(np.int64)
+    factors = {k: _seeded_factors(n, m, k, 200 + k) for k in (8, 64)}
+
+    def fit(eng, k, rows=None):
+        U0, V0 = factors[k]
+        eng.set_factors(U0 if rows is None else U0[rows], V0)
+        iters, trace = eng.fit(None, flags=flags, trace=True, **FIT)
+        U, V = eng.get_factors()
+        out = dict(iters=int(iters), trace=trace, U=U, V=V)
+        if variant == "e_rows":
+            out["P"] = eng.e_step(THRESH)
+        bal = eng.balance_info()
+        out.update(packed=repr(eng.packed_info()), passes=repr(eng.pass_info()), item_entries=bal["item_entries"],
+                   n_items=bal["n_items"])
+        return out
+
+    def engine():
+        eng = amd.Engine()
+        if variant == "reference":
+            eng.set_arithmetic("reference")
+        eng.upload_csr(X)
+        return eng
+
+    fresh = {}
+    for key, k, rows in (("k8", 8, None), ("k64", 64, None), ("resample", 8, idx)):
+        with engine() as eng:
+            if rows is not None:
+                eng.bootstrap(rows)
+            fresh[key] = fit(eng, k, rows)
+    assert fresh["k8"]["item_entries"] == 8 and fresh["k8"]["n_items"] == int(np.ceil(X.getnnz(axis=0) / 8.0).sum())
+    assert (fresh["k64"]["item_entries"], fresh["k64"]["n_items"]) == (fresh["k8"]["item_entries"], fresh["k8"]["n_items"])
+    # the document pass does run over row items, several to a row: the longest document has more entries than an item holds
+    assert X.getnnz(axis=1).max() >= 9 * int(BUILDER_KNOBS["PLSA_ROW_SEG"])
+    if variant != "reference":                          # (the reference arithmetic has its own document pass)
+        with engine() as eng:
+            eng.timing(True)
+            fit(eng, 8)
+            assert "k_row_reduce" in set(eng.timing_report()), sorted(eng.timing_report())
+    not_built = repr(dict(csr=None, csc=None))
+    assert fresh["k8"]["packed"] == (repr(dict(csr=None, csc="packed")) if variant == "reference" else
+                                     repr(dict(csr="packed", csc="packed")))
+    differs = []
+
+    def compare(got, want, what):                       # every key on its own: one difference does not hide the next
+        assert sorted(got) == sorted(want)
+        for key in sorted(got):
+            try:
+                assert_same({key: got[key]}, {key: want[key]}, what)
+            except AssertionError as e:
+                differs.append(str(e))
+
+    with engine() as eng:
+        compare(fit(eng, 8), fresh["k8"], "k=8 on a fresh upload")
+        compare(fit(eng, 64), fresh["k64"], "k=64 after k=8 on the same upload")
+        eng.release_scratch()
+        after_release = dict(fresh["k8"], packed=not_built) if variant == "reference" else fresh["k8"]
+        compare(fit(eng, 8), after_release, "k=8 after release_scratch")
+        eng.bootstrap(idx)
+        compare(fit(eng, 8, idx), fresh["resample"], "k=8 on a bootstrap resample")
+        eng.bootstrap(None)
+        compare(fit(eng, 8), fresh["k8"], "k=8 on the base corpus again")
+    assert not differs, "\n".join(differs)
 
 
 @pytest.mark.gpu

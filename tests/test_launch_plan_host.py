@@ -31,12 +31,12 @@ def program(tmp_path_factory):
     return exe
 
 
-def call(program, name, cases):
-    """one line per case in, one line of integers per case out"""
-    text = "".join("%s %s\n" % (name, " ".join(v.hex() if isinstance(v, float) else str(int(v)) for v in case)) for case in cases)
+def call(program, name, cases, parse=int):
+    """one line per case in, one line of integers (parse=float.fromhex: of hex floats) per case out"""
+    text = "".join("%s %s\n" % (name, " ".join(float(v).hex() if isinstance(v, float) else str(int(v)) for v in case)) for case in cases)
     out = subprocess.run([program], input=text, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-4000:]
-    rows = [[int(v) for v in line.split()] for line in out.stdout.splitlines()]
+    rows = [[parse(v) for v in line.split()] for line in out.stdout.splitlines()]
     assert len(rows) == len(cases)
     return rows
 
@@ -164,3 +164,149 @@ def test_wide_tables_and_the_xcd_split_rule(program):
     # from 64 chunks on, and only when P(z|d) exceeds 2 MiB: 8192 rows of 64 floats are exactly 2 MiB; PLSA_XCD_SPLIT=0
     assert call(program, "xcd_split", [(1, 63, 1000000, 64), (1, 64, 1000000, 64), (1, 64, 8192, 64), (1, 64, 8193, 64),
                                        (0, 64, 1000000, 64), (1, 1000, 18846, 20)]) == [[0], [1], [0], [1], [0], [0]]
+
+
+# ------------------------------------------------------------------------------------------------
+# the arithmetic of the structure builders (csrc/plsa_structures.hpp): sort bits, piece lengths, the packing rule
+# ------------------------------------------------------------------------------------------------
+def edge_counts(limit=2 ** 31 - 2):
+    """1, 2, 3 and every 2^j - 1, 2^j, 2^j + 1 up to the largest count an upload may have"""
+    values = {1, 2, 3, limit}
+    for j in range(1, 32):
+        values.update((2 ** j - 1, 2 ** j, 2 ** j + 1))
+    return sorted(v for v in values if 1 <= v <= limit)
+
+
+def test_sort_bits_cover_every_key(program):
+    counts = edge_counts()
+    assert counts[-1] == 2 ** 31 - 2 and 2 ** 30 + 1 in counts
+    for m, (bits,) in zip(counts, call(program, "sort_bits", [(m,) for m in counts])):
+        assert bits == max(1, (m - 1).bit_length()), m
+        assert m - 1 < 2 ** bits, m                      # the property: the largest column id fits
+    cases = [(n, band) for n in counts for band in (0, 64, 8192)]
+    for (n, band), (len_bits, key_bits) in zip(cases, call(program, "order_key", cases)):
+        assert len_bits == max(1, n.bit_length()), (n, band)
+        band_bits = next(b for b in range(1, 64) if 2 ** b >= n // band + 1) if band else 0
+        assert key_bits == len_bits + band_bits, (n, band)
+        # the largest key an item can get: the last band over the longest inverted length; band 0: the last document
+        largest = (((n - 1) // band) << len_bits) | (2 ** len_bits - 1) if band else n - 1
+        assert largest < 2 ** key_bits and key_bits <= 64, (n, band, key_bits)
+        assert 2 ** len_bits - 1 - n >= 0, (n, len_bits)  # a column of n entries still has an inverted length
+
+
+def test_packing_rule_and_e_step_piece_length(program):
+    ids = 2 ** 24
+    cases = [(0, 10, 0), (1, 10, 0), (100, ids, 0), (100, ids + 1, 0),
+             (161, 10, 10), (160, 10, 10), (159, 10, 10)]        # 16 escapes: nnz - 1, nnz, nnz + 1
+    assert call(program, "packed_ok", cases) == [[0], [1], [1], [0], [1], [1], [0]]
+    by_lanes = {1: 16, 2: 16, 4: 16, 8: 8, 16: 64, 32: 64, 64: 64}
+    cases = [(lpn, override) for lpn in by_lanes for override in (-1, 0, 48)]
+    for (lpn, override), (seg,) in zip(cases, call(program, "e_item_len", cases)):
+        assert seg == (by_lanes[lpn] if override < 0 else override), (lpn, override)
+
+
+# ------------------------------------------------------------------------------------------------
+# the balance controller of the XCD stretches: stamps -> XCD times and spread, times -> next fractions
+# ------------------------------------------------------------------------------------------------
+EQUAL = [x / 8.0 for x in range(9)]
+
+
+def xcd_times_restated(stamps, grid):
+    t0 = min(s for s in stamps if s)
+    us = [max(1.0, (max(stamps[b] for b in range(grid) if b % 8 == x) - t0) / 100.0) for x in range(8)]
+    return us, (max(us) - min(us)) / (sum(us) / 8.0)
+
+
+def test_xcd_times_from_hand_made_stamps(program):
+    start = 5_000_000_000
+    # 20 workgroups: XCD x = b % 8 has b = x, x + 8 (and x + 16 for x < 4); [20] is the start stamp
+    a = [start + 100 * (300 + 7 * b) for b in range(20)] + [start]
+    a[3] = 0                                             # a workgroup that never stamped: XCD 3's time is 11's or 19's
+    b = list(a)
+    b[20] = 0                                            # no start stamp: the earliest end stamp is the origin ...
+    b[0] = start + 50                                    # ... and XCD 0 ...
+    b[8] = b[16] = start + 100                           # ... ends half a microsecond after it: the floor of 1 us
+    c = [start + 100 * 1000] * 8 + [start]               # one workgroup per XCD, all at 1000 us: no spread
+    for stamps in (a, b, c):
+        grid = len(stamps) - 1
+        (got,) = call(program, "xcd_times", [(grid, *stamps)], parse=float.fromhex)
+        us, spread = xcd_times_restated(stamps, grid)
+        assert got[:8] == us, (got, us)
+        assert abs(got[8] - spread) <= 1e-12 * max(spread, 1.0), (got[8], spread)
+    us, spread = xcd_times_restated(a, 20)
+    assert us == [300.0 + 7 * 16, 300.0 + 7 * 17, 300.0 + 7 * 18, 300.0 + 7 * 19, 300.0 + 7 * 12, 300.0 + 7 * 13, 300.0 + 7 * 14,
+                  300.0 + 7 * 15]
+    assert xcd_times_restated(b, 20)[0][0] == 1.0 and xcd_times_restated(c, 8) == ([1000.0] * 8, 0.0)
+
+
+def step_restated(frac, us):
+    import numpy as np
+    us = np.asarray(us, np.float64)
+    size = np.maximum(1e-6, np.diff(np.asarray(frac, np.float64)) * (1.0 + 0.8 * (us.mean() / us - 1.0)))
+    return [0.0] + list(np.cumsum(size) / size.sum())
+
+
+def steps(program, cases):
+    return call(program, "balance_step", [tuple(frac) + tuple(us) for frac, us in cases], parse=float.fromhex)
+
+
+def check_boundaries(program, fracs):
+    """every stretch list a step produced gives chunk boundaries that start at 0, end at n_chunks and never go back"""
+    cases = [(n, *frac) for n in (64, 65, 4096) for frac in fracs]
+    for (n, *frac), got in zip(cases, call(program, "balance", cases)):
+        lo = got[:9]
+        assert lo[0] == 0 and lo[8] == n and all(lo[x] <= lo[x + 1] for x in range(8)), (n, frac, lo)
+
+
+def test_balance_step_keeps_equal_times_and_stays_a_partition(program):
+    import numpy as np
+    # (a) equal times: nothing to correct
+    skewed = [0.0, 0.9, 0.91, 0.92, 0.93, 0.94, 0.95, 0.96, 1.0]
+    cases = [(frac, [t] * 8) for frac in (EQUAL, skewed) for t in (1.0, 100.0, 8000.0, 1e6)]
+    for (frac, _), got in zip(cases, steps(program, cases)):
+        assert max(abs(g - f) for g, f in zip(got, frac)) <= 1e-15, (frac, got)
+    # (b) any times, any stretches: still a partition of the list
+    rs = np.random.RandomState(2024)
+    cases = []
+    for _ in range(1000):
+        frac = [0.0] + sorted(rs.uniform(0.0, 1.0, size=7).tolist()) + [1.0]
+        cases.append((frac, np.exp(rs.uniform(0.0, np.log(1e6), size=8)).tolist()))
+    assert all(1.0 <= t <= 1e6 for _, us in cases for t in us)
+    produced = steps(program, cases)
+    for (frac, us), got in zip(cases, produced):
+        assert got[0] == 0.0 and got[8] == 1.0 and all(got[x] < got[x + 1] for x in range(8)), (frac, us, got)
+        assert max(abs(g - w) for g, w in zip(got, step_restated(frac, us))) <= 1e-12, (frac, us, got)
+    check_boundaries(program, produced)                  # (d)
+
+
+def test_balance_converges_within_the_launches_it_is_given(program):
+    """Driven from equal stretches like ensure_balance drives it -- measure, stop at a spread of 2 %, else step -- the controller
+    is done within the eight measurements a first structure gets (a NumPy restatement needs 2 or 3 steps for these inputs)."""
+    def slowness(s):
+        return lambda f: [8000.0 * (f[x + 1] - f[x]) * s[x] for x in range(8)]
+
+    def density(a):                                      # cost density 1 + a u over the list: the integral over a stretch
+        return lambda f: [8000.0 * ((f[x + 1] - f[x]) + 0.5 * a * (f[x + 1] ** 2 - f[x] ** 2)) for x in range(8)]
+    models = [slowness(s) for s in ([1, 1, 1, 1, 1, 1, 1, 2], [1, 1.1, 0.9, 1, 1.2, 1, 0.8, 1], [3, 1, 1, 1, 1, 1, 1, 1])] + \
+             [density(a) for a in (0.5, 1.0, 3.0)]
+    fracs = [list(EQUAL) for _ in models]
+    reached = [0] * len(models)
+    produced = []
+    for measurement in range(1, 9):
+        pending = []
+        for i, model in enumerate(models):
+            if reached[i]:
+                continue
+            us = [max(1.0, t) for t in model(fracs[i])]
+            if (max(us) - min(us)) / (sum(us) / 8.0) <= 0.02:
+                reached[i] = measurement
+            else:
+                pending.append((i, us))
+        if not pending or measurement == 8:
+            break
+        for (i, _), got in zip(pending, steps(program, [(fracs[i], us) for i, us in pending])):
+            fracs[i] = got
+            produced.append(got)
+    assert all(reached), reached
+    assert reached[0] > 1, "the first model starts out of balance"
+    check_boundaries(program, produced)                  # (d)
