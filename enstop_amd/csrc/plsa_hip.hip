@@ -38,6 +38,8 @@
 #include "../../include/plsa_hip_nmf.h"
 #include "mt_jump.hpp"
 #include "plsa_embed_kernels.hpp"
+#include "plsa_init_kernels.hpp"
+#include "plsa_init_plan.hpp"
 #include "plsa_kernels.hpp"
 #include "plsa_launch_plan.hpp"
 #include "plsa_member_kernels.hpp"
@@ -1301,221 +1303,7 @@ int plsa_download_active_csr(plsa_ctx *c, int32_t *indptr, int32_t *indices, flo
     return 0;
 }
 
-int plsa_set_factors(plsa_ctx *c, const float *U, const float *V, int64_t n, int64_t m, int32_t k) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->n <= 0) return fail(c, "plsa_set_factors: upload a corpus first");
-    if (n != c->n || m != c->m)
-        return fail(c, "plsa_set_factors: factor shapes (n=%lld, m=%lld) do not match the active matrix (%lld x %lld)",
-                    (long long)n, (long long)m, (long long)c->n, (long long)c->m);
-    if (k <= 0 || k > 1024) return fail(c, "plsa_set_factors: k=%d outside [1,1024]", k);
-    if (!U) return fail(c, "plsa_set_factors: U is NULL");
-    if (!V && (k != c->k || !c->Vt[0].p)) return fail(c, "plsa_set_factors: V is NULL but no topics with k=%d are resident", k);
-    set_shape(c, k);
-    const int kp = c->kp;
-    c->fac_n = n; c->fac_m = m;
-    for (int i = 0; i < 2; ++i) CHK(ensure(c, c->U[i], sizeof(float) * (size_t)n * kp));
-    for (int i = 0; i < 2; ++i) CHK(ensure(c, c->Vt[i], sizeof(float) * (size_t)m * kp));
-    CHK(ensure(c, c->Vacc, sizeof(float) * (size_t)m * kp));
-    c->p_state.invalidate();
-    c->cu = 0;
-    if (kp != k) HIPCHK(c, hipMemsetAsync(c->U[0].p, 0, sizeof(float) * (size_t)n * kp, c->stream));
-    if (kp == k)
-        CHK(copy_to_device(c, c->U[0].p, U, sizeof(float) * (size_t)n * k));
-    else
-        HIPCHK(c, hipMemcpy2DAsync(c->U[0].p, sizeof(float) * kp, U, sizeof(float) * k, sizeof(float) * k,
-                                   (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (V) {
-        c->cv = 0;
-        CHK(ensure(c, c->tmp0, sizeof(float) * (size_t)k * m));
-        HIPCHK(c, hipMemcpyAsync(c->tmp0.p, V, sizeof(float) * (size_t)k * m, hipMemcpyHostToDevice, c->stream));
-        dim3 grid((unsigned)((m + 31) / 32), (unsigned)((kp + 31) / 32));
-        hipLaunchKernelGGL(plsa::k_v_to_vt, grid, dim3(256), 0, c->stream, c->tmp0.as<float>(),
-                           c->Vt[0].as<float>(), k, (int)m, kp);
-        CHK(launch_check(c, "k_v_to_vt"));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// Throughput-mode initialisation on the device (counter-based RNG; not the reference's stream).
-int plsa_init_factors_device(plsa_ctx *c, int32_t k, uint64_t seed) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->n <= 0) return fail(c, "plsa_init_factors_device: upload a corpus first");
-    if (k <= 0 || k > 1024) return fail(c, "plsa_init_factors_device: k=%d outside [1,1024]", k);
-    const i64 n = c->n, m = c->m;
-    set_shape(c, k);
-    const int kp = c->kp;
-    c->fac_n = n; c->fac_m = m;
-    for (int i = 0; i < 2; ++i) CHK(ensure(c, c->U[i], sizeof(float) * (size_t)n * kp));
-    for (int i = 0; i < 2; ++i) CHK(ensure(c, c->Vt[i], sizeof(float) * (size_t)m * kp));
-    CHK(ensure(c, c->Vacc, sizeof(float) * (size_t)m * kp));
-    c->p_state.invalidate(); c->cu = 0; c->cv = 0;
-    // P(w|z): uniform draws per (topic, word), topic rows normalised -> generate [k, m] then transpose
-    CHK(ensure(c, c->tmp0, sizeof(float) * (size_t)std::max<i64>(k, 4) * m));
-    hipLaunchKernelGGL(plsa::k_init_rows, dim3(grid_for(c, k, 4)), dim3(256), 0, c->stream, c->tmp0.as<float>(),
-                       (i64)k, (int)m, (int)m, (unsigned long long)plsa::mix64(seed ^ 0x5157ull));
-    dim3 grid((unsigned)((m + 31) / 32), (unsigned)((kp + 31) / 32));
-    hipLaunchKernelGGL(plsa::k_v_to_vt, grid, dim3(256), 0, c->stream, c->tmp0.as<float>(), c->Vt[0].as<float>(), k, (int)m, kp);
-    hipLaunchKernelGGL(plsa::k_init_rows, dim3(grid_for(c, n, 4)), dim3(256), 0, c->stream, c->U[0].as<float>(),
-                       n, k, kp, (unsigned long long)plsa::mix64(seed ^ 0xD0C5ull));
-    CHK(launch_check(c, "k_init_rows"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// plsa_init(X, k, init="random", rng) + the float32 casts of plsa_fit (plsa.py:455-456, 510-511,
-// 709-710) with the reference's own MT19937 stream, evaluated on the device.  state_io: the 624 key
-// words + position of numpy.random.RandomState.get_state(); on return it holds the advanced state.
-// V_host == nullptr: plsa_init (topics drawn first, then the document rows).  V_host != nullptr: the
-// refit initialisation (plsa.py:979-981) -- only rand(n, k) is drawn, the topics are the given ones.
-static int mt_init(plsa_ctx *c, int32_t k, uint32_t *state_io /*[625]*/, const float *V_host) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->n <= 0) return fail(c, "plsa_init_factors_mt19937: upload a corpus first");
-    if (k <= 0 || k > 1024) return fail(c, "plsa_init_factors_mt19937: k=%d outside [1,1024]", k);
-    if (state_io[624] > 624) return fail(c, "plsa_init_factors_mt19937: bad generator position");
-    const i64 n = c->n, m = c->m;
-    set_shape(c, k);
-    const int kp = c->kp;
-    c->fac_n = n; c->fac_m = m;
-    for (int i = 0; i < 2; ++i) CHK(ensure(c, c->U[i], sizeof(float) * (size_t)n * kp));
-    for (int i = 0; i < 2; ++i) CHK(ensure(c, c->Vt[i], sizeof(float) * (size_t)m * kp));
-    CHK(ensure(c, c->Vacc, sizeof(float) * (size_t)m * kp));
-    c->p_state.invalidate(); c->cu = 0; c->cv = 0;
-    const i64 v_doubles = V_host ? 0 : (i64)k * m;
-    const i64 n_doubles = v_doubles + n * (i64)k;
-    const i64 n_words = 2 * n_doubles;
-    // Split the stream into pieces that start 2^b blocks apart (csrc/mt_jump.hpp) once it is long
-    // enough to pay for the jumps; the words produced are those of the one sequential stream.
-    const int pos0 = (int)state_io[624];
-    const i64 first = std::min<i64>(624 - pos0, n_words);
-    const i64 total_blocks = (n_words - first + 623) / 624;
-    i64 per_stream = std::max<i64>(total_blocks, 1);
-    int n_streams = 1, log2_per = 0;
-    if (c->mt_streams > 1 && total_blocks >= c->mt_min_blocks) {
-        while (((i64)1 << log2_per) * c->mt_streams < total_blocks) ++log2_per;
-        per_stream = (i64)1 << log2_per;
-        n_streams = (int)((total_blocks + per_stream - 1) / per_stream);
-    }
-    int streams_p2 = 1, levels = 0;
-    while (streams_p2 < n_streams) { streams_p2 *= 2; ++levels; }
-    std::vector<uint32_t> polys((size_t)levels * 624);
-    for (int l = 0; l < levels; ++l)        // level l jumps by (streams_p2 >> (l+1)) * per_stream blocks
-        if (!mtjump::block_jump_polynomial(log2_per + (levels - 1 - l), polys.data() + (size_t)l * 624))
-            return fail(c, "plsa_init_factors_mt19937: MT19937 characteristic polynomial not recovered");
-    DevBuf &words = c->mt_words, &st = c->mt_state, &fin = c->mt_fin, &gp = c->mt_poly;
-    CHK(ensure(c, words, sizeof(unsigned) * (size_t)n_words));
-    CHK(ensure(c, st, sizeof(unsigned) * 624 * (size_t)streams_p2));
-    CHK(ensure(c, fin, sizeof(unsigned) * 640 + sizeof(double) * 1024));
-    if (levels) CHK(ensure(c, gp, sizeof(unsigned) * polys.size()));
-    if (!V_host && !c->mt_chain)     // chunk sums (u64), parity pairs (2 x u64), tile sums (f64) and binade guesses (int) of the topic marginals
-        CHK(ensure(c, c->mt_seq, (size_t)k * (size_t)((m + plsa::MT_SEQ_L - 1) / plsa::MT_SEQ_L) * (3 * sizeof(plsa::u64) + sizeof(int) + sizeof(double))));
-    hipError_t e = hipMemsetAsync(st.p, 0, sizeof(unsigned) * 624 * (size_t)streams_p2, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(st.p, state_io, sizeof(unsigned) * 624, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && levels)
-        e = hipMemcpyAsync(gp.p, polys.data(), sizeof(unsigned) * polys.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        if (levels) {
-            Scope s(c, "k_mt_jump");
-            for (int l = 0; l < levels; ++l) {
-                const int step = streams_p2 >> (l + 1);
-                hipLaunchKernelGGL(plsa::k_mt_jump, dim3((unsigned)(streams_p2 / (2 * step)), plsa::MT_JUMP_SLICES), dim3(256), 0,
-                                   c->stream, gp.as<unsigned>() + (size_t)l * 624, st.as<unsigned>(), step, n_streams);
-            }
-        }
-        { Scope s(c, "k_mt19937_fill");
-          hipLaunchKernelGGL(plsa::k_mt19937_fill, dim3((unsigned)n_streams), dim3(PLSA_MT_THREADS), 0, c->stream,
-                             st.as<unsigned>(), words.as<unsigned>(), pos0, per_stream, n_words, n_streams, fin.as<unsigned>()); }
-        if (V_host) {
-            float *Vtmp = reinterpret_cast<float *>(c->Vt[1].p);     // [m*kp] floats >= k*m: free scratch here
-            e = hipMemcpyAsync(Vtmp, V_host, sizeof(float) * (size_t)k * m, hipMemcpyHostToDevice, c->stream);
-            dim3 grid((unsigned)((m + 31) / 32), (unsigned)((kp + 31) / 32));
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(plsa::k_v_to_vt, grid, dim3(256), 0, c->stream, Vtmp, c->Vt[0].as<float>(), k, (int)m, kp);
-        } else {
-            // V[k, m] in the reference layout (words are consumed in that order), then the layout transpose
-            float *Vtmp = reinterpret_cast<float *>(c->Vt[1].p);     // [m*kp] floats >= k*m: free scratch here
-            double *marg = reinterpret_cast<double *>(fin.as<unsigned>() + 632) ;   // k <= 1024 doubles behind the state
-            if (c->mt_chain) {       // PLSA_MT_CHAIN=1: the plain chain of m dependent adds per topic (A/B, tests)
-                hipLaunchKernelGGL(plsa::k_mt_marginal_v, dim3((unsigned)k), dim3(64), 0, c->stream, words.as<unsigned>(), k, (int)m, marg);
-            } else {                 // the same roundings from per-chunk parity pairs (plsa_kernels.hpp: k_mt_chunk_pairs)
-                const int nch = (int)((m + plsa::MT_SEQ_L - 1) / plsa::MT_SEQ_L);
-                const size_t per = (size_t)k * nch;
-                plsa::u64 *csum = c->mt_seq.as<plsa::u64>(), *pairs = csum + per;
-                double *tsum = reinterpret_cast<double *>(pairs + 2 * per);          // [k][tiles] <= per doubles
-                int *guess = reinterpret_cast<int *>(tsum + per);
-                const dim3 tiles((unsigned)((nch + plsa::MT_SEQ_L - 1) / plsa::MT_SEQ_L), (unsigned)k);
-                hipLaunchKernelGGL(plsa::k_mt_chunk_sums, tiles, dim3(64), 0, c->stream, words.as<unsigned>(), (int)m, nch, csum, tsum);
-                hipLaunchKernelGGL(plsa::k_mt_chunk_pairs, tiles, dim3(64), 0, c->stream, words.as<unsigned>(), (int)m, nch,
-                                   csum, tsum, pairs, guess);
-                hipLaunchKernelGGL(plsa::k_mt_marginal_walk, dim3((unsigned)k), dim3(64), 0, c->stream, words.as<unsigned>(),
-                                   (int)m, nch, pairs, guess, marg);
-            }
-            hipLaunchKernelGGL(plsa::k_mt_scale_v, dim3(grid_for(c, (i64)k * m, 256)), dim3(256), 0, c->stream,
-                               words.as<unsigned>(), marg, k, (int)m, Vtmp);
-            dim3 grid((unsigned)((m + 31) / 32), (unsigned)((kp + 31) / 32));
-            hipLaunchKernelGGL(plsa::k_v_to_vt, grid, dim3(256), 0, c->stream, Vtmp, c->Vt[0].as<float>(), k, (int)m, kp);
-        }
-        hipLaunchKernelGGL(plsa::k_mt_init_u, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                           words.as<unsigned>(), v_doubles, n, k, kp, c->U[0].as<float>());
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(state_io, fin.p, sizeof(unsigned) * 625, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, "plsa_init_factors_mt19937: %s", hipGetErrorString(e));
-    return 0;
-}
-
-int plsa_init_factors_mt19937(plsa_ctx *c, int32_t k, uint32_t *state_io /*[625]*/) {
-    if (!state_io) return fail(c, "plsa_init_factors_mt19937: state_io is NULL");
-    return mt_init(c, k, state_io, nullptr);
-}
-
-int plsa_mt_marginals(plsa_ctx *c, double *out, int32_t k) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!out || k <= 0 || k > 1024 || !c->mt_fin.p || k != c->k)
-        return fail(c, "plsa_mt_marginals: no MT19937 initialisation with k=%d on this context", k);
-    HIPCHK(c, hipMemcpy(out, c->mt_fin.as<unsigned>() + 632, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int plsa_refit_init_mt19937(plsa_ctx *c, const float *V, int64_t m, int32_t k, uint32_t *state_io /*[625]*/) {
-    if (!state_io || !V) return fail(c, "plsa_refit_init_mt19937: NULL argument");
-    if (m != c->m) return fail(c, "plsa_refit_init_mt19937: topics have %lld words, the active matrix %lld", (long long)m, (long long)c->m);
-    return mt_init(c, k, state_io, V);
-}
-
-int plsa_get_factors(plsa_ctx *c, float *U, float *V) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (V) {        // transposed on the device first: it is in flight while P(z|d) travels
-        CHK(ensure(c, c->tmp0, sizeof(float) * (size_t)c->k * c->m));
-        dim3 grid((unsigned)((c->m + 31) / 32), (unsigned)((c->kp + 31) / 32));
-        hipLaunchKernelGGL(plsa::k_vt_to_v, grid, dim3(256), 0, c->stream, c->Vt[c->cv].as<float>(),
-                           c->tmp0.as<float>(), c->k, (int)c->m, c->kp);
-        CHK(launch_check(c, "k_vt_to_v"));
-    }
-    if (U) {
-        if (c->kp == c->k)      // rows are contiguous: one linear copy (the strided 2-D form ran at 10 GB/s from 1 M x 64)
-            CHK(copy_to_host(c, U, c->U[c->cu].p, sizeof(float) * (size_t)c->n * c->k));
-        else
-            HIPCHK(c, hipMemcpy2DAsync(U, sizeof(float) * c->k, c->U[c->cu].p, sizeof(float) * c->kp,
-                                       sizeof(float) * c->k, (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (V) CHK(copy_to_host(c, V, c->tmp0.p, sizeof(float) * (size_t)c->k * c->m));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int plsa_copy_components_to_device(plsa_ctx *c, void *dst) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    dim3 grid((unsigned)((c->m + 31) / 32), (unsigned)((c->kp + 31) / 32));
-    hipLaunchKernelGGL(plsa::k_vt_to_v, grid, dim3(256), 0, c->stream, c->Vt[c->cv].as<float>(),
-                       reinterpret_cast<float *>(dst), c->k, (int)c->m, c->kp);
-    CHK(launch_check(c, "k_vt_to_v"));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
+#include "plsa_init.hpp"      // factors onto a context and off it: host factors, device initialisation, the MT19937 stream
 
 int plsa_set_arithmetic(plsa_ctx *c, int32_t mode) {
     if (mode & ~(PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL))
@@ -2328,14 +2116,6 @@ int plsa_cluster_representatives(plsa_ctx *c, const float *topics, int64_t t, in
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n_clusters * m, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, "plsa_cluster_representatives: %s", hipGetErrorString(e));
-    return 0;
-}
-
-int plsa_host_mt19937_jump(uint32_t *key, int32_t log2_blocks) {
-    if (!key || log2_blocks < 0 || log2_blocks > 40) return 1;
-    uint32_t g[624];
-    if (!mtjump::block_jump_polynomial(log2_blocks, g)) return 1;
-    mtjump::apply_jump(key, g);
     return 0;
 }
 

@@ -689,8 +689,8 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_ref_norm_chain(const int *__r
 
 // ------------------------------------------------------------------------------------------------
 // The same chain WITHOUT nnz dependent additions: norm_pwz[z] from per-chunk (parity -> increment) pairs, the technique of
-// k_mt_chunk_pairs / k_mt_marginal_walk (plsa_kernels.hpp; there: float64 sums of 53-bit draws) carried over to float32 sums of
-// arbitrary non-negative float32 addends.
+// k_mt_chunk_pairs / k_mt_marginal_walk (plsa_init_kernels.hpp; there: float64 sums of 53-bit draws) carried over to float32 sums
+// of arbitrary non-negative float32 addends.
 //
 // While the running sum S stays inside one binade [2^e, 2^(e+1)) it is an integer multiple M of u = 2^(e-23), 2^23 <= M < 2^24, and
 // one rounded addition of t = mt * 2^(Et - 150) (mt the 24-bit significand, Et the biased exponent, 1 for denormals) is

@@ -31,7 +31,7 @@ int plsa_init_factors_device(plsa_ctx *ctx, int32_t k, uint64_t seed);
 
 /* Diagnostics: the k float64 topic marginals (enstop/utils.py:24-29, `marginal[i] += ndarray[i, j]` left to right) that the
  * last plsa_init_factors_mt19937 call divided by.  The device evaluates that sequential sum from per-chunk parity pairs
- * (csrc/plsa_kernels.hpp: k_mt_chunk_pairs); the tests pin it bit for bit to numpy's own sequential accumulation.   */
+ * (csrc/plsa_init_kernels.hpp: k_mt_chunk_pairs); the tests pin it bit for bit to numpy's own sequential accumulation. */
 int plsa_mt_marginals(plsa_ctx *ctx, double *out, int32_t k);
 
 /* uploads a host P(z|w,d) [nnz,k] in place of plsa_e_step's output (lets plsa_m_step be tested in isolation against

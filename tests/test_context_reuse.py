@@ -925,6 +925,66 @@ def test_error_then_reuse(amd, baselines, kind):
                 assert_same(got, baselines.get(name, k, op, arg), "%s after %s on %s" % (op, kind, name))
 
 
+@pytest.mark.gpu
+def test_initialisation_kinds_on_one_context(amd):
+    """Host factors, the MT19937 stream, host document rows over the resident topics, the device generator and the refit
+    initialisation, one after the other on one context: every way in sizes the factor buffers and resets the parities and
+    P(z|w,d) in one place (plsa_init.hpp: alloc_factors), so after each step the context holds, bit for bit, what a fresh
+    context holds after that step alone.  k = 6, 33, 6, 20, 6 pads to 8, 36, 8, 20 (no padding), 8: the lane shape changes in
+    both directions."""
+    X = _random_corpus(130, 70, 0.1, _seed("init kinds"))
+    n, m = X.shape
+    U6, V6 = _seeded_factors(n, m, 6, 61)
+    U6b, V6b = _seeded_factors(n, m, 6, 62)
+    U6c, _ = _seeded_factors(n, m, 6, 63)
+
+    def read(eng, **more):
+        U, V = eng.get_factors()
+        return dict(U=U, V=V, **more)
+
+    def two_iterations(eng):
+        iters, trace = eng.fit(None, n_iter=2, n_iter_per_test=1, tolerance=0.0, flags=amd.PLSA_FUSED, trace=True)
+        return read(eng, iters=int(iters), trace=trace)
+
+    def host(eng):
+        return read(eng.set_factors(U6, V6)), None
+
+    def stream(eng):
+        rng = np.random.RandomState(_seed("init kinds", 33))
+        got = read(eng.init_factors_numpy_stream(33, rng), next_draw=float(rng.rand()))
+        return got, two_iterations(eng)
+
+    def rows_only(eng):
+        eng.set_factors(U6b, V6b)
+        got = read(eng.set_factors(U6c))
+        assert np.array_equal(_bits(got["V"]), _bits(V6b)) and np.array_equal(_bits(got["U"]), _bits(U6c))
+        return got, None
+
+    def device(eng):
+        return read(eng.init_factors_device(20, seed=77)), None
+
+    def refit_stream(eng):
+        rng = np.random.RandomState(_seed("init kinds", 6))
+        got = read(eng.init_factors_numpy_stream(6, rng, topics=V6), next_draw=float(rng.rand()))
+        assert np.array_equal(_bits(got["V"]), _bits(V6))
+        return got, two_iterations(eng)
+
+    steps = (host, stream, rows_only, device, refit_stream)
+    fresh = []
+    for step in steps:
+        with amd.Engine() as eng:
+            eng.upload_csr(X)
+            fresh.append(step(eng))
+    assert [(f[0]["U"].shape[1], lane_shape(f[0]["U"].shape[1])[0]) for f in fresh] == [(6, 8), (33, 36), (6, 8), (20, 20), (6, 8)]
+    with amd.Engine() as eng:
+        eng.upload_csr(X)
+        for step, (want, want_fit) in zip(steps, fresh):
+            got, got_fit = step(eng)
+            assert_same(got, want, "%s after the steps before it" % step.__name__)
+            if want_fit is not None:
+                assert_same(got_fit, want_fit, "two fused iterations after %s" % step.__name__)
+
+
 def _planted(n, m, k_true, seed):
     rs = np.random.RandomState(seed)
     topics = rs.dirichlet(np.full(m, 0.03), size=k_true)

@@ -1,4 +1,4 @@
-"""Host model of the arithmetic behind k_mt_chunk_pairs / k_mt_marginal_walk (csrc/plsa_kernels.hpp): a left-to-right
+"""Host model of the arithmetic behind k_mt_chunk_pairs / k_mt_marginal_walk (csrc/plsa_init_kernels.hpp): a left-to-right
 float64 sum of non-negative multiples of 2^-53 below 1 -- the reference's `marginal[i] += ndarray[i, j]`, utils.py:24-29,
 over numpy's random_sample draws -- evaluated from per-chunk (start parity -> increment) pairs must reproduce the
 sequential roundings bit for bit, ties (round half to even) included.  The GPU tests pin the kernels themselves to
