@@ -152,8 +152,13 @@ NMF_SIGNATURES = {
     "plsa_nmf_fit": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.POINTER(_i32), _vp, _i32]),
 }
 
+# include/plsa_hip_score.h: per-document log-likelihood / held-out scoring (its own table as well)
+SCORE_SIGNATURES = {
+    "plsa_score_rows": (C.c_int, [_ctx, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
-HW_QUEUES = {"set_by": None, "hip_mapped_before_load": None}
+HW_QUEUES ={"set_by": None, "hip_mapped_before_load": None}
 
 
 def _default_hw_queues():
@@ -202,7 +207,7 @@ def load():
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
-            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()):
+            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

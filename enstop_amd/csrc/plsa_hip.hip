@@ -36,6 +36,7 @@
 #include "../../include/plsa_hip_blocked.h"
 #include "../../include/plsa_hip_embed.h"
 #include "../../include/plsa_hip_nmf.h"
+#include "../../include/plsa_hip_score.h"
 #include "mt_jump.hpp"
 #include "plsa_embed_kernels.hpp"
 #include "plsa_init_kernels.hpp"
@@ -266,6 +267,9 @@ struct plsa_ctx {
     // KL-divergence NMF (plsa_nmf.hpp): W_sum / H_sum as float64 [2][kp] and guarded float32 [2][kp], the slab sums they are
     // added up from, the objective's per-workgroup partials and its result.  W and H themselves live in U[cu] / Vt[cv]
     struct Nmf { DevBuf raw, guarded, slabs, obj, out; } nmf;
+    // plsa_score_rows (plsa_score.hpp): the CSR arrays of ANOTHER matrix with the active matrix's shape, the validation flag
+    // and the three per-document sums [3][n].  Kept between calls, freed by plsa_release_scratch; never part of the corpus
+    struct Score { DevBuf indptr, col, val, flag, out; } score;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -1726,7 +1730,8 @@ int plsa_release_scratch(plsa_ctx *c) {
                       &c->mt_words, &c->mt_state, &c->mt_fin, &c->mt_poly, &c->mt_seq,
                       // member stack + gather buffers of the ensemble exchange (16 runs x 64 topics x 100 k words = 0.4 GB):
                       // re-created by the next plsa_stack_reserve / plsa_comm_allgather_stack
-                      &c->comm_stack, &c->comm_recv, &c->comm_send, &c->metric_mask, &c->metric_small})
+                      &c->comm_stack, &c->comm_recv, &c->comm_send, &c->metric_mask, &c->metric_small,
+                      &c->score.indptr, &c->score.col, &c->score.val, &c->score.flag, &c->score.out})
         b->release();
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
@@ -2263,3 +2268,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_drivers.hpp"   // plsa_fit, plsa_refit: backends of the likelihood-test loop (plsa_fit_schedule.hpp)
 #include "plsa_members.hpp"   // batched ensemble members (include/plsa_hip_members.h)
 #include "plsa_nmf.hpp"       // KL-divergence NMF (include/plsa_hip_nmf.h)
+#include "plsa_score_kernels.hpp"   // held-out scoring (include/plsa_hip_score.h): the document-owned pass ...
+#include "plsa_score.hpp"           // ... and its host side

@@ -318,6 +318,41 @@ class Engine:
         self._ok(self._L.plsa_log_likelihood(self._h, ptr(sw), C.byref(out)))
         return out.value
 
+    # -- held-out scoring (include/plsa_hip_score.h) ---------------------------------------------------
+    def score_rows(self, other=None, sample_weight=None):
+        """Per-document (ll, tokens, unscored), float64 [n] each, under the factors in force: the log-likelihood terms of
+        log_likelihood summed per document over the entries with x > 0 and a positive model probability, the weighted
+        count of those entries, and the weighted count of the entries whose word the model gives no mass.  other=None
+        scores the active matrix; a scipy matrix of the active matrix's shape is scored against the same factors from
+        scratch buffers and leaves the resident corpus, the factors and every derived structure as they were.  Values
+        are cast to float32 like upload_csr's; a bad shape, column id or row pointer is a ValueError."""
+        n, m, _ = self.shape
+        sw = None if sample_weight is None else _f32(sample_weight)
+        if sw is not None and sw.shape != (n,):
+            raise ValueError("sample_weight has shape %s, expected (%d,)" % (sw.shape, n))
+        indptr = indices = data = None
+        nnz = 0
+        if other is not None:
+            other = other.tocsr()
+            if other.shape != (n, m):
+                raise ValueError("the other matrix has shape %s, the active matrix (and the factors) %s"
+                                 % (other.shape, (n, m)))
+            if other.nnz > 2**31 - 64:
+                raise ValueError("matrix too large for 32-bit indices: %d x %d with %d stored entries (limit 2^31 - 64 entries)"
+                                 % (n, m, other.nnz))
+            indptr = np.ascontiguousarray(other.indptr, dtype=np.int32)
+            indices = np.ascontiguousarray(other.indices, dtype=np.int32)
+            data = _f32(other.data)
+            nnz = data.shape[0]
+        ll, tokens, unscored = (np.empty(n, np.float64) for _ in range(3))
+        if self._L.plsa_score_rows(self._h, ptr(indptr), ptr(indices), ptr(data), nnz, ptr(sw), ptr(ll), ptr(tokens),
+                                   ptr(unscored)):
+            msg = self._L.plsa_last_error(self._h).decode()
+            if "column index" in msg or "indptr" in msg:
+                raise ValueError("column index out of range" if "column index" in msg and "indptr is" not in msg else msg)
+            raise DeviceError(msg)
+        return ll, tokens, unscored
+
     # -- EM drivers --------------------------------------------------------------------------------
     def _drive(self, fn, sample_weight, n_iter, n_iter_per_test, tolerance, thresh, flags, trace):
         sw = None if sample_weight is None else _f32(sample_weight)

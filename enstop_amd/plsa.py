@@ -352,10 +352,21 @@ def plsa_refit(X, topics, sample_weight, n_iter=50, n_iter_per_test=10, toleranc
         flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
     if not issparse(X):
         X = csr_matrix(X)
+    eng = get_engine(device)
+    iters, ll = _refit_on_engine(eng, X, topics, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh,
+                                 check_random_state(random_state), flags, trace=return_info, p_budget=p_budget)
+    U, _ = eng.get_factors(want_v=False)
+    if return_info:
+        return U, dict(n_iter=iters, log_likelihood_trace=ll)
+    return U
+
+
+def _refit_on_engine(eng, X, topics, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh, rng, flags=None,
+                     trace=False, p_budget=None):
+    """plsa_refit's body on `eng`, whose lock the caller holds: X becomes the resident corpus, P(z|d) is drawn from `rng`
+    and folded in against the fixed `topics`, and both stay on the device (scoring.held_out_scores goes on from there)."""
     topics = np.asarray(topics)
     k = topics.shape[0]
-    rng = check_random_state(random_state)
-    eng = get_engine(device)
     eng.upload_csr(X)
     device_init = os.environ.get("ENSTOP_AMD_HOST_INIT", "auto")
     if isinstance(rng, np.random.RandomState) and (
@@ -372,11 +383,7 @@ def plsa_refit(X, topics, sample_weight, n_iter=50, n_iter_per_test=10, toleranc
     if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
         sw = np.asarray(sample_weight, np.float32)
     with _PBudget(eng, p_budget):
-        iters, ll = eng.refit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=return_info)
-    U, _ = eng.get_factors(want_v=False)
-    if return_info:
-        return U, dict(n_iter=iters, log_likelihood_trace=ll)
-    return U
+        return eng.refit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=trace)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -401,7 +408,40 @@ class _TopicMetricsMixin:
         return self._metric(topic_num, n_words, log_lift, mean_log_lift)
 
 
-class PLSA(_TopicMetricsMixin, BaseEstimator, TransformerMixin):
+class _ScoringMixin:
+    """score_samples() / score() / perplexity() of a fitted model on documents X (scoring.held_out_scores), what
+    scikit-learn's own topic model offers.  The fold-in uses the estimator's `components_`, `transform_random_seed`,
+    flags and `device`, and transform's fixed n_iter=50, n_iter_per_test=5, tolerance=0.001."""
+
+    def _held_out(self, X, method, fraction=0.5, on_zero="inf"):
+        from .scoring import held_out_scores
+        X = check_array(X, accept_sparse="csr")
+        flags = self._flags() if hasattr(self, "_flags") else None
+        return held_out_scores(X, self.components_, method=method, fraction=fraction,
+                               random_state=self.transform_random_seed, n_iter=50, n_iter_per_test=5, tolerance=0.001,
+                               device=self.device, flags=flags, on_zero=on_zero)
+
+    def score_samples(self, X):
+        """log P(document) [n] of every document of X under its OWN fold-in: P(z|d) is fitted on the very tokens that are
+        scored (what transform(X) returns), so this is the optimistic fold-in likelihood, not a held-out one -- use
+        perplexity(method="completion") for that.  -inf where a document holds a word the model gives no mass; 0 for an
+        empty document."""
+        s = self._held_out(X, "fold_in")
+        return np.where(s["unscored"] > 0, -np.inf, s["log_likelihood"])
+
+    def score(self, X, y=None):
+        """sum of score_samples(X): the fold-in log-likelihood of X, higher is better"""
+        return float(np.sum(self.score_samples(X)))
+
+    def perplexity(self, X, method="completion", fraction=0.5, on_zero="inf"):
+        """exp(-log-likelihood per token) of X.  "completion": every document is split (scoring.split_documents,
+        `fraction` of its tokens observed), P(z|d) is folded in on the observed part and the held-out part is scored;
+        "fold_in": both on all of X (optimistic).  on_zero="inf": inf when a scored document holds a word the model gives
+        no mass; "skip": those tokens are left out."""
+        return self._held_out(X, method, fraction, on_zero)["perplexity"]
+
+
+class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
     """Probabilistic Latent Semantic Analysis with the reference estimator's constructor, methods
     and fitted attributes (enstop/plsa.py:1000-1285): `components_` = P(w|z) [k, m],
     `embedding_` = P(z|d) [n, k], `training_data_`.  Additive: `n_iter_` (EM iterations run),
