@@ -1,5 +1,5 @@
 """ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h,
-plsa_hip_metrics.h, plsa_hip_blocked.h, plsa_hip_embed.h and plsa_hip_nmf.h).
+plsa_hip_metrics.h, plsa_hip_blocked.h, plsa_hip_embed.h, plsa_hip_nmf.h, plsa_hip_score.h and plsa_hip_tempered.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -106,6 +106,7 @@ SIGNATURES = {
     "plsa_generate_synthetic_topics": (C.c_int, [_ctx, _i64, _i64, _i64, C.c_double, C.c_uint64, _i32, C.c_double,
                                                  C.c_double, C.POINTER(_i64)]),
     "plsa_synthetic_dominant_topics": (C.c_int, [_ctx, _i32p]),
+    "plsa_temper_factors": (C.c_int, [_ctx, C.c_double, _vp, _vp]),
 }
 
 # include/plsa_hip_members.h: batched ensemble members (a table of its own: SIGNATURES is the two headers above, exactly)
@@ -155,6 +156,14 @@ NMF_SIGNATURES = {
 # include/plsa_hip_score.h: per-document log-likelihood / held-out scoring (its own table as well)
 SCORE_SIGNATURES = {
     "plsa_score_rows": (C.c_int, [_ctx, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+}
+
+# include/plsa_hip_tempered.h: tempered EM and the factor snapshot slot (its own table as well)
+TEMPERED_SIGNATURES = {
+    "plsa_fit_tempered": (C.c_int, [_ctx, _vp, C.c_double, _i32, _i32, C.c_double, C.c_float, _i32, C.POINTER(_i32), _vp,
+                                    C.POINTER(_i32)]),
+    "plsa_factors_snapshot": (C.c_int, [_ctx]),
+    "plsa_factors_restore": (C.c_int, [_ctx]),
 }
 
 _lib = None
@@ -207,7 +216,8 @@ def load():
     _default_hw_queues()
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
-            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()):
+            list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + \
+            list(TEMPERED_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

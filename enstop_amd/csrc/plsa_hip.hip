@@ -37,6 +37,7 @@
 #include "../../include/plsa_hip_embed.h"
 #include "../../include/plsa_hip_nmf.h"
 #include "../../include/plsa_hip_score.h"
+#include "../../include/plsa_hip_tempered.h"
 #include "mt_jump.hpp"
 #include "plsa_embed_kernels.hpp"
 #include "plsa_init_kernels.hpp"
@@ -270,6 +271,15 @@ struct plsa_ctx {
     // plsa_score_rows (plsa_score.hpp): the CSR arrays of ANOTHER matrix with the active matrix's shape, the validation flag
     // and the three per-document sums [3][n].  Kept between calls, freed by plsa_release_scratch; never part of the corpus
     struct Score { DevBuf indptr, col, val, flag, out; } score;
+    // tempered EM (plsa_tempered.hpp): the two side tables U^beta [n, kp] and Vt^beta [m, kp] of the iteration in flight, and
+    // the one snapshot slot of plsa_factors_snapshot with the shape it was taken for.  4 kp (n + m) bytes each, kept between
+    // calls, freed by plsa_release_scratch
+    struct Tempered {
+        DevBuf U, Vt, snapU, snapVt;
+        bool have_snap = false;
+        i64 snap_n = 0, snap_m = 0;
+        int snap_k = 0;
+    } tempered;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -1731,8 +1741,10 @@ int plsa_release_scratch(plsa_ctx *c) {
                       // member stack + gather buffers of the ensemble exchange (16 runs x 64 topics x 100 k words = 0.4 GB):
                       // re-created by the next plsa_stack_reserve / plsa_comm_allgather_stack
                       &c->comm_stack, &c->comm_recv, &c->comm_send, &c->metric_mask, &c->metric_small,
-                      &c->score.indptr, &c->score.col, &c->score.val, &c->score.flag, &c->score.out})
+                      &c->score.indptr, &c->score.col, &c->score.val, &c->score.flag, &c->score.out,
+                      &c->tempered.U, &c->tempered.Vt, &c->tempered.snapU, &c->tempered.snapVt})
         b->release();
+    c->tempered.have_snap = false;
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
     // gather that needs a larger one, or plsa_destroy.
@@ -2270,3 +2282,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_nmf.hpp"       // KL-divergence NMF (include/plsa_hip_nmf.h)
 #include "plsa_score_kernels.hpp"   // held-out scoring (include/plsa_hip_score.h): the document-owned pass ...
 #include "plsa_score.hpp"           // ... and its host side
+#include "plsa_tempered_kernels.hpp"   // tempered EM (include/plsa_hip_tempered.h): the power of a factor table ...
+#include "plsa_tempered.hpp"           // ... and the loop, the snapshot slot and the diagnostic read-back

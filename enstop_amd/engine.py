@@ -376,6 +376,37 @@ class Engine:
         return self._drive(self._L.plsa_refit, sample_weight, n_iter, n_iter_per_test, tolerance,
                            e_step_thresh, flags, trace)
 
+    # -- tempered EM (include/plsa_hip_tempered.h) ----------------------------------------------------
+    def fit_tempered(self, beta, sample_weight=None, n_iter=100, n_iter_per_test=10, tolerance=0.001,
+                     e_step_thresh=1e-32, flags=None, trace=False):
+        """fit() with the responsibilities flattened by the exponent 0 < beta <= 1: every iteration raises the factors to
+        the power beta into two side tables and runs the fused iteration on those.  Same loop, stop rule and return
+        values as fit; every likelihood is the likelihood of the true factors.  beta == 1.0 is fit().  Fused default
+        arithmetic only: anything else is a DeviceError that launches nothing."""
+        flags = default_flags() if flags is None else flags
+
+        def fn(h, sw, *rest):
+            return self._L.plsa_fit_tempered(h, sw, float(beta), *rest)
+        return self._drive(fn, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace)
+
+    def temper_factors(self, beta):
+        """(P(z|d)^beta [n, k], P(w|z)^beta [k, m]): the side tables a tempered iteration at beta forms from the factors in
+        force, which stay as they are (diagnostics / tests)."""
+        n, m, _ = self.shape
+        U, V = np.empty((n, self.k), np.float32), np.empty((self.k, m), np.float32)
+        self._ok(self._L.plsa_temper_factors(self._h, float(beta), ptr(U), ptr(V)))
+        return U, V
+
+    def snapshot_factors(self):
+        """Copy the factors in force into the engine's one snapshot slot (device to device)."""
+        self._ok(self._L.plsa_factors_snapshot(self._h))
+        return self
+
+    def restore_factors(self):
+        """The snapshot becomes the factors in force again; DeviceError without one, or after the shape or k changed."""
+        self._ok(self._L.plsa_factors_restore(self._h))
+        return self
+
     # -- doc-sharded fit building blocks ---------------------------------------------------------------
     def em_accumulate(self, sample_weight=None, e_step_thresh=1e-32, want_ll=False, materialised=False):
         """materialised: the reference's kernel sequence over this context's rows (E-step into P(z|w,d), M-step from it)

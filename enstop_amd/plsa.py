@@ -447,6 +447,11 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
     `embedding_` = P(z|d) [n, k], `training_data_`.  Additive: `n_iter_` (EM iterations run),
     and the `device` constructor keyword at the end of the signature.
 
+    `tempering` (additive; None: off, nothing changes): "auto" fits by tempered EM with held-out early stopping
+    (enstop_amd.tempered: a tenth of every document's tokens decides when to stop and when to lower beta), a float in
+    (0, 1] fits all of X at that fixed beta.  Sets `beta_`, `n_iter_`, `validation_perplexity_`, `tempering_report_`.
+    Default arithmetic only; the other estimators of this module refuse it.
+
     `p_budget`: bytes that P(z|w,d) may take in fit / transform with `arithmetic="reference"` (plsa_fit; None: the
     ENSTOP_AMD_P_BUDGET_MB environment variable, unset: no budget); no effect outside the reference arithmetic.
 
@@ -457,10 +462,11 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
 
     def __init__(self, n_components=10, init="random", n_iter=100, n_iter_per_test=10,
                  tolerance=0.001, e_step_thresh=1e-32, transform_random_seed=42, random_state=None,
-                 device=None, arithmetic=None, p_budget=None):
+                 device=None, arithmetic=None, p_budget=None, tempering=None):
         self.n_components = n_components
         self.arithmetic = arithmetic
         self.p_budget = p_budget
+        self.tempering = tempering
         self.init = init
         self.n_iter = n_iter
         self.n_iter_per_test = n_iter_per_test
@@ -471,15 +477,57 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
         self.device = device
 
     _extra_flags = 0      # subclasses: stop-test variant of the reference module they stand in for
+    tempering = None      # (class default: estimators unpickled from before the parameter existed, and the subclasses)
 
     def _flags(self):
         # arithmetic="reference": the reference's float32 sums, rounding for rounding (engine.arithmetic_flags)
         return default_flags() | self._extra_flags | arithmetic_flags(getattr(self, "arithmetic", None))
 
+    # `tempering` is listed among the parameters only while it is set: the parameter lists of existing pipelines, grids and
+    # pickles are what they were, and clone() still carries a value that was given
+    def get_params(self, deep=True):
+        params = super().get_params(deep)
+        if params.get("tempering", None) is None:
+            params.pop("tempering", None)
+        return params
+
+    def set_params(self, **params):
+        if "tempering" in params:
+            self.tempering = params.pop("tempering")
+        return super().set_params(**params) if params else self
+
     def _fit_factors(self, X, sample_weight):
+        if getattr(self, "tempering", None) is not None:
+            return self._fit_factors_tempered(X, sample_weight)
         return plsa_fit(X, self.n_components, sample_weight, self.init, self.n_iter, self.n_iter_per_test,
                         self.tolerance, self.e_step_thresh, self.random_state, device=self.device,
                         flags=self._flags(), return_info=True, p_budget=getattr(self, "p_budget", None))
+
+    def _fit_factors_tempered(self, X, sample_weight):
+        """tempering="auto": tempered.plsa_fit_tempered (a share of every document held out, beta lowered and the fit stopped
+        by its perplexity; n_iter and n_iter_per_test are the schedule's budget and burst length).  A float in (0, 1]: all
+        of X fitted at that fixed beta with the usual likelihood stop."""
+        from . import tempered
+        t = self.tempering
+        if type(self) is not PLSA:
+            raise ValueError("tempering is offered by PLSA only, not by %s" % type(self).__name__)
+        if arithmetic_flags(getattr(self, "arithmetic", None)):
+            raise ValueError("tempering has no form in the reference arithmetic (arithmetic=%r)" % (self.arithmetic,))
+        if isinstance(t, str):
+            if t != "auto":
+                raise ValueError('tempering must be None, "auto" or a float in (0, 1], not %r' % (t,))
+            U, V, report = tempered.plsa_fit_tempered(
+                X, self.n_components, sample_weight, self.init, n_iter_per_test=self.n_iter_per_test, n_iter=self.n_iter,
+                e_step_thresh=self.e_step_thresh, transform_random_seed=self.transform_random_seed,
+                random_state=self.random_state, device=self.device, flags=self._flags())
+            self.beta_, self.validation_perplexity_ = report["selected_beta"], report["selected_perplexity"]
+            self.tempering_report_ = report
+            return U, V, dict(n_iter=report["selected_iteration"])
+        U, V, info = tempered.plsa_fit_fixed_beta(
+            X, self.n_components, t, sample_weight, self.init, self.n_iter, self.n_iter_per_test, self.tolerance,
+            self.e_step_thresh, self.random_state, device=self.device, flags=self._flags())
+        self.beta_, self.validation_perplexity_, self.tempering_report_ = float(t), None, info
+        return U, V, info
 
     def fit(self, X, y=None, sample_weight=None):
         self.fit_transform(X, sample_weight=sample_weight)

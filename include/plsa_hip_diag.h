@@ -141,6 +141,12 @@ int plsa_generate_synthetic_topics(plsa_ctx *ctx, int64_t n, int64_t m, int64_t 
  * of document d's mixture theta_d (tests: does a fit recover the planted structure; experiments: document orderings). */
 int plsa_synthetic_dominant_topics(plsa_ctx *ctx, int32_t *out /* [n], host */);
 
+/* ---- tempered EM (plsa_hip_tempered.h) ---------------------------------------------------------------
+ * The side tables of one tempered iteration at `beta` (0 < beta <= 1), formed from the current factors exactly as that
+ * iteration forms them and read back in plsa_get_factors' layouts: U_out [n, k] = P(z|d)^beta, V_out [k, m] = P(w|z)^beta
+ * (either may be NULL).  The factors stay as they are.  Tests need the exact bits of the tables.               */
+int plsa_temper_factors(plsa_ctx *ctx, double beta, float *U_out, float *V_out);
+
 #ifdef __cplusplus
 }
 #endif
