@@ -9,13 +9,14 @@ no sample weights anywhere in the fit, stop test `change / |cur| < tolerance` on
 """
 import numpy as np
 
-from .engine import PLSA_STOP_NO_ZERO_ARM, default_flags
+from ._driver import resolve_flags
+from .engine import PLSA_STOP_NO_ZERO_ARM
 from .plsa import BlockParallelPLSA, plsa_fit as _plsa_fit  # noqa: F401
 
 
 def plsa_fit(X, k, n_row_blocks=8, n_col_blocks=8, init="random", n_iter=100, n_iter_per_test=10,
              tolerance=0.001, e_step_thresh=1e-32, random_state=None, device=None, flags=None,
              return_info=False):
-    flags = (default_flags() if flags is None else flags) | PLSA_STOP_NO_ZERO_ARM
     return _plsa_fit(X, k, np.ones(X.shape[0], np.float32), init, n_iter, n_iter_per_test, tolerance,
-                     e_step_thresh, random_state, device=device, flags=flags, return_info=return_info)
+                     e_step_thresh, random_state, device=device, flags=resolve_flags(flags, extra=PLSA_STOP_NO_ZERO_ARM),
+                     return_info=return_info)

@@ -60,14 +60,49 @@ def arithmetic_flags(arithmetic):
 def default_flags():
     """Fit schedule: fused (P(z|w,d) never touches HBM) unless ENSTOP_AMD_MATERIALISE=1, which
     follows the reference's E-step -> M-step kernel sequence through a materialised nnz x k array.
-    ENSTOP_AMD_ARITHMETIC=reference / reference_source selects the reference's rounding (arithmetic_flags)
-    for every fit that does not say otherwise."""
+    ENSTOP_AMD_ARITHMETIC=reference / reference_source adds the reference's rounding (arithmetic_flags).
+    These are the flags of a fit that is given none (_driver.resolve_flags); explicit `flags=` replace them, and
+    StreamedPLSA starts from PLSA_FUSED without consulting either variable."""
     flags = 0 if os.environ.get("ENSTOP_AMD_MATERIALISE", "0") == "1" else PLSA_FUSED
     return flags | arithmetic_flags(os.environ.get("ENSTOP_AMD_ARITHMETIC") or None)
 
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _mt19937_state(rng):
+    """(uint32[625]: MT19937 key and position, which the device advances in place; put_back(): writes them into `rng`)"""
+    kind, key, pos, has_gauss, cached = rng.get_state()
+    if kind != "MT19937":
+        raise ValueError("not an MT19937 RandomState")
+    state = np.empty(625, np.uint32)
+    state[:624] = key
+    state[624] = pos
+    return state, lambda: rng.set_state((kind, state[:624].copy(), int(state[624]), has_gauss, cached))
+
+
+def _csr_arrays(X):
+    """(indptr int32, indices int32, data float32), contiguous, of a scipy matrix (any dtype; values are cast like
+    plsa.py:714).  The device layout is the reference's: int32 row pointers / indices (plsa.py:26 `i4[::1]`, its loop
+    counters are uint32).  scipy switches to int64 index arrays on its own for large matrices: what does not fit is
+    refused instead of letting the casts wrap around."""
+    X = X.tocsr()
+    n, m = X.shape
+    if X.nnz > 2**31 - 64 or max(n, m) >= 2**31 - 1:
+        raise ValueError("matrix too large for 32-bit indices: %d x %d with %d stored entries (limit 2^31 - 64 entries)"
+                         % (n, m, X.nnz))
+    return (np.ascontiguousarray(X.indptr, dtype=np.int32), np.ascontiguousarray(X.indices, dtype=np.int32), _f32(X.data))
+
+
+def _csr_failure(msg, pointer_text_wins=False):
+    """The exception for the error text of plsa_upload_csr / plsa_score_rows: a violated index contract (k_validate_csr,
+    or the row pointers' ends) is the reference-style ValueError, everything else a DeviceError.  A bad column id reads
+    "column index out of range" -- unless, for score_rows (pointer_text_wins), the row pointers are out of order as well."""
+    if "column index" in msg or "indptr" in msg:
+        short = "column index" in msg and not (pointer_text_wins and "indptr is" in msg)
+        return ValueError("column index out of range" if short else msg)
+    return DeviceError(msg)
 
 
 class Engine:
@@ -81,6 +116,7 @@ class Engine:
         self.k = 0
         self.base_rows = 0
         self.p_budget = 0              # set_p_budget
+        self.arithmetic_bits = 0       # set_arithmetic (the C context has no getter: this record is what scoped calls restore)
         # a context is not thread-safe: callers that share the process-wide engine (the reference is
         # driven from dask/joblib thread pools, enstop_.py:209-217) serialise on this lock
         self.lock = threading.RLock()
@@ -123,25 +159,13 @@ class Engine:
     # -- corpus ----------------------------------------------------------------------------------
     def upload_csr(self, X):
         """X: scipy CSR (any dtype; values are cast to float32 like plsa.py:714)."""
-        X = X.tocsr()
         n, m = X.shape
-        # the device layout is the reference's: int32 row pointers / indices (plsa.py:26 `i4[::1]`, its loop counters are
-        # uint32).  scipy switches to int64 index arrays on its own for large matrices: refuse what does not fit
-        # instead of letting the cast below wrap around
-        if X.nnz > 2**31 - 64 or max(n, m) >= 2**31 - 1:
-            raise ValueError("matrix too large for 32-bit indices: %d x %d with %d stored entries (limit 2^31 - 64 entries)"
-                             % (n, m, X.nnz))
-        indptr = np.ascontiguousarray(X.indptr, dtype=np.int32)
-        indices = np.ascontiguousarray(X.indices, dtype=np.int32)
-        data = _f32(X.data)
+        indptr, indices, data = _csr_arrays(X)
         # the index contract (0 <= column < m, row pointers non-decreasing) is checked ON THE DEVICE by one streaming pass over
         # the copy (k_validate_csr): a host-side min() / max() over the indices of config 3 cost more than the upload itself
         # (62 ms for 100 M entries on the build container).  A violation is the reference-style ValueError either way.
         if self._L.plsa_upload_csr(self._h, indptr, indices, data, n, m, data.shape[0]):
-            msg = self._L.plsa_last_error(self._h).decode()
-            if "column index" in msg or "indptr" in msg:
-                raise ValueError("column index out of range" if "column index" in msg else msg)
-            raise DeviceError(msg)
+            raise _csr_failure(self._L.plsa_last_error(self._h).decode())
         self.base_rows = n
         return self
 
@@ -213,12 +237,7 @@ class Engine:
         numpy.random.RandomState, MT19937) exactly as rng.rand(k, m); rng.rand(n, k) would; `rng`
         is left in the state the host path would leave it in.  With `topics` ([k, m], fixed) only
         rng.rand(n, k) is drawn: the initialisation of plsa_refit (plsa.py:979-981)."""
-        kind, key, pos, has_gauss, cached = rng.get_state()
-        if kind != "MT19937":
-            raise ValueError("not an MT19937 RandomState")
-        state = np.empty(625, np.uint32)
-        state[:624] = key
-        state[624] = pos
+        state, put_back = _mt19937_state(rng)
         if topics is None:
             self._ok(self._L.plsa_init_factors_mt19937(self._h, int(k), state))
         else:
@@ -226,7 +245,7 @@ class Engine:
             if V.shape[0] != int(k):
                 raise ValueError("topics have %d rows, expected k=%d" % (V.shape[0], int(k)))
             self._ok(self._L.plsa_refit_init_mt19937(self._h, ptr(V), V.shape[1], int(k), state))
-        rng.set_state((kind, state[:624].copy(), int(state[624]), has_gauss, cached))
+        put_back()
         self.k = int(k)
         return self
 
@@ -291,7 +310,9 @@ class Engine:
     # -- kernel-level operators --------------------------------------------------------------------
     def set_arithmetic(self, arithmetic=None):
         """Arithmetic of e_step / m_step / log_likelihood and of later fits on this engine (arithmetic_flags)."""
-        self._ok(self._L.plsa_set_arithmetic(self._h, arithmetic_flags(arithmetic)))
+        bits = arithmetic_flags(arithmetic)
+        self._ok(self._L.plsa_set_arithmetic(self._h, bits))
+        self.arithmetic_bits = bits
         return self
 
     def e_step(self, thresh=1e-32, out=None, want_host_copy=True):
@@ -333,24 +354,15 @@ class Engine:
         indptr = indices = data = None
         nnz = 0
         if other is not None:
-            other = other.tocsr()
             if other.shape != (n, m):
                 raise ValueError("the other matrix has shape %s, the active matrix (and the factors) %s"
                                  % (other.shape, (n, m)))
-            if other.nnz > 2**31 - 64:
-                raise ValueError("matrix too large for 32-bit indices: %d x %d with %d stored entries (limit 2^31 - 64 entries)"
-                                 % (n, m, other.nnz))
-            indptr = np.ascontiguousarray(other.indptr, dtype=np.int32)
-            indices = np.ascontiguousarray(other.indices, dtype=np.int32)
-            data = _f32(other.data)
+            indptr, indices, data = _csr_arrays(other)
             nnz = data.shape[0]
         ll, tokens, unscored = (np.empty(n, np.float64) for _ in range(3))
         if self._L.plsa_score_rows(self._h, ptr(indptr), ptr(indices), ptr(data), nnz, ptr(sw), ptr(ll), ptr(tokens),
                                    ptr(unscored)):
-            msg = self._L.plsa_last_error(self._h).decode()
-            if "column index" in msg or "indptr" in msg:
-                raise ValueError("column index out of range" if "column index" in msg and "indptr is" not in msg else msg)
-            raise DeviceError(msg)
+            raise _csr_failure(self._L.plsa_last_error(self._h).decode(), pointer_text_wins=True)
         return ll, tokens, unscored
 
     # -- EM drivers --------------------------------------------------------------------------------
@@ -358,6 +370,7 @@ class Engine:
         sw = None if sample_weight is None else _f32(sample_weight)
         ll = np.zeros(n_iter + 2, np.float32)
         iters, nll = C.c_int32(0), C.c_int32(0)
+        flags = default_flags() if flags is None else flags
         if trace:
             flags |= PLSA_TRACE_LL
         self._ok(fn(self._h, ptr(sw), int(n_iter), int(n_iter_per_test), float(tolerance),
@@ -366,13 +379,11 @@ class Engine:
 
     def fit(self, sample_weight=None, n_iter=100, n_iter_per_test=10, tolerance=0.001,
             e_step_thresh=1e-32, flags=None, trace=False):
-        flags = default_flags() if flags is None else flags
         return self._drive(self._L.plsa_fit, sample_weight, n_iter, n_iter_per_test, tolerance,
                            e_step_thresh, flags, trace)
 
     def refit(self, sample_weight=None, n_iter=50, n_iter_per_test=10, tolerance=0.005,
               e_step_thresh=1e-32, flags=None, trace=False):
-        flags = default_flags() if flags is None else flags
         return self._drive(self._L.plsa_refit, sample_weight, n_iter, n_iter_per_test, tolerance,
                            e_step_thresh, flags, trace)
 
@@ -383,8 +394,6 @@ class Engine:
         the power beta into two side tables and runs the fused iteration on those.  Same loop, stop rule and return
         values as fit; every likelihood is the likelihood of the true factors.  beta == 1.0 is fit().  Fused default
         arithmetic only: anything else is a DeviceError that launches nothing."""
-        flags = default_flags() if flags is None else flags
-
         def fn(h, sw, *rest):
             return self._L.plsa_fit_tempered(h, sw, float(beta), *rest)
         return self._drive(fn, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace)
@@ -814,14 +823,9 @@ class MemberBatch:
             idx = np.ascontiguousarray(idx, dtype=np.int64)
             ip, n_out = idx.ctypes.data, idx.shape[0]
         if rng is not None:
-            kind, key, pos, has_gauss, cached = rng.get_state()
-            if kind != "MT19937":
-                raise ValueError("not an MT19937 RandomState")
-            state = np.empty(625, np.uint32)
-            state[:624] = key
-            state[624] = pos
+            state, put_back = _mt19937_state(rng)
             self.eng._ok(self._L.plsa_members_prepare(self._b, int(member), ip, n_out, int(k), state.ctypes.data, None, None))
-            rng.set_state((kind, state[:624].copy(), int(state[624]), has_gauss, cached))
+            put_back()
         else:
             U, V = _f32(U), _f32(V)
             if U.ndim != 2 or V.ndim != 2 or U.shape[1] != int(k) or V.shape[0] != int(k):

@@ -33,7 +33,7 @@ non-finite entries for them before that file existed) and t * m above 2^32 eleme
 import numpy as np
 from scipy.sparse import csr_matrix, issparse
 from sklearn.base import BaseEstimator, TransformerMixin
-from sklearn.utils import check_array, check_random_state
+from sklearn.utils import check_array
 
 from .enstop_ import ensemble_of_topics
 from .plsa import _ScoringMixin, _TopicMetricsMixin, plsa_refit
@@ -275,9 +275,4 @@ class EnsembleTopics(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, Transform
         return U
 
     def transform(self, X, y=None):
-        X = check_array(X, accept_sparse="csr")
-        random_state = check_random_state(self.transform_random_seed)
-        X = csr_matrix(X) if not issparse(X) else X.tocsr()
-        sample_weight = _check_sample_weight(None, X, dtype=np.float32)
-        return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5,
-                          tolerance=0.001, random_state=random_state, device=self.device)
+        return self._transform(X)

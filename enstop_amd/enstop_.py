@@ -15,6 +15,7 @@ from sklearn.utils import check_random_state
 import os
 import threading
 
+from ._driver import apply_init_slot, plan_init, resolve_flags
 from .engine import get_engine, get_member_engines
 from .plsa import _fit_on_engine, _locked
 
@@ -33,12 +34,8 @@ CONCURRENT_MEMBERS_CELLS = float(os.environ.get("ENSTOP_AMD_CONCURRENT_MEMBERS_C
 
 
 def _member_flags(kwargs):
-    """`flags=` and / or `arithmetic=` of plsa_topics / ensemble_of_topics -> the flags of the members' fits (None: defaults)"""
-    from .engine import arithmetic_flags, default_flags
-    flags, arithmetic = kwargs.get("flags", None), kwargs.get("arithmetic", None)
-    if arithmetic is None:
-        return flags
-    return (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
+    """`flags=` and / or `arithmetic=` of plsa_topics / ensemble_of_topics -> the flags of the members' fits"""
+    return resolve_flags(kwargs.get("flags", None), kwargs.get("arithmetic", None))
 
 
 def concurrent_members(nnz, k, n_jobs):
@@ -69,10 +66,8 @@ def batch_members_cap():
 def _batch_eligible(eng, A, k, member_kw):
     """What a batch carries: the fused schedule in the engine's own arithmetic, eager and untimed, on a corpus small
     enough that one fit leaves the GPU idle.  Everything else takes the contexts (same results)."""
-    from ._lib import PLSA_FUSED, PLSA_REFERENCE_LL, PLSA_REFERENCE_SUMS, PLSA_SHARDED
-    from .engine import default_flags
-    PLSA_GRAPH = 128
-    flags = default_flags() if member_kw.get("flags") is None else int(member_kw["flags"])
+    from ._lib import PLSA_FUSED, PLSA_GRAPH, PLSA_REFERENCE_LL, PLSA_REFERENCE_SUMS, PLSA_SHARDED
+    flags = resolve_flags(member_kw.get("flags"))
     if not flags & PLSA_FUSED or flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL | PLSA_SHARDED | PLSA_GRAPH):
         return False
     if os.environ.get("PLSA_GRAPH", "0") not in ("", "0") or getattr(eng, "timing_on", False):
@@ -85,29 +80,17 @@ def _batch_eligible(eng, A, k, member_kw):
     return member_kw.get("n_iter", 100) > 0
 
 
-def _prepare_member(batch, j, eng, k, bootstrap=True, random_state=None, init="random", **_unused):
-    """`_member_on_engine` + `_fit_on_engine` up to the fit, for slot j of a batch: the bootstrap draw, then the same stream
-    into the initialisation (on the device from the MT19937 state when the factors are large, host plsa_init otherwise)."""
-    from .plsa import plsa_init
-    n_base = eng.base_rows
-    idx = None
-    if bootstrap:
-        rng = check_random_state(random_state)                       # enstop_.py:86
-        idx = rng.randint(0, n_base, size=n_base)                    # enstop_.py:87
-    rng = check_random_state(random_state)
-    n, m = n_base, batch.eng.shape[1]
-    device_init = os.environ.get("ENSTOP_AMD_HOST_INIT", "auto")
-    use_device_init = device_init == "0" or (device_init == "auto" and k * (n + m) >= 262_144)
-    if isinstance(init, str) and init == "random" and isinstance(rng, np.random.RandomState) and use_device_init:
-        batch.prepare(j, k, idx=idx, rng=rng)
-        return
+def _bootstrap_rows(n_base, bootstrap, random_state):
+    """The member's resample of the corpus rows, the first draw of its stream (enstop_.py:86-87); None: the corpus itself"""
+    return check_random_state(random_state).randint(0, n_base, size=n_base) if bootstrap else None
 
-    class _Shape:
-        pass
-    Xs = _Shape()
-    Xs.shape = (n, m)
-    U, V = plsa_init(Xs, k, init=init, rng=rng)
-    batch.prepare(j, k, idx=idx, U=U.astype(np.float32, order="C"), V=V.astype(np.float32, order="C"))
+
+def _prepare_member(batch, j, eng, k, bootstrap=True, random_state=None, init="random", **_unused):
+    """What `_member_on_engine` does before its fit, for slot j of a batch: the bootstrap draw, then the same stream into
+    the initialisation plsa_fit would choose (_driver.plan_init)."""
+    idx = _bootstrap_rows(eng.base_rows, bootstrap, random_state)
+    plan = plan_init(eng.base_rows, batch.eng.shape[1], k, init, check_random_state(random_state))
+    apply_init_slot(batch, j, k, plan, idx)
 
 
 def _fit_members_batched(eng, A, k, runs, seeds, member_kw, world, n_runs, B, slots_wanted=0):
@@ -177,13 +160,7 @@ def _member_on_engine(eng, k, bootstrap=True, random_state=None, init="random", 
                       n_iter_per_test=10, tolerance=0.001, e_step_thresh=1e-16, flags=None, stack_dst=None):
     """One ensemble member on a corpus already uploaded to `eng`; returns P(w|z) [k, m] -- or, with
     `stack_dst` (a device address), leaves it there and returns None."""
-    n_base = eng.base_rows
-    if bootstrap:
-        rng = check_random_state(random_state)                       # enstop_.py:86
-        idx = rng.randint(0, n_base, size=n_base)                    # enstop_.py:87
-        eng.bootstrap(idx)                                           # enstop_.py:88 (on device)
-    else:
-        eng.bootstrap(None)
+    eng.bootstrap(_bootstrap_rows(eng.base_rows, bootstrap, random_state))   # enstop_.py:88, on the device
     # sample_weight is all ones (enstop_.py:91); random_state is passed on unchanged, so a
     # RandomState instance continues its stream into the factor initialisation while an int
     # re-seeds it (enstop_.py:101,113 + plsa.py:707)

@@ -16,14 +16,14 @@ anywhere, calling anything needs libplsa_hip.so and a gfx950 device.
   plsa_refit_inner / plsa_refit :820 / :923 plsa_refit_inner / plsa_refit -> plsa_refit (C ABI)
   PLSA                         :1000        PLSA
 """
-import os
-
 import numpy as np
 from scipy.sparse import csr_matrix, issparse
 from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array, check_random_state
 
-from .engine import PLSA_SW_LL_ONLY, PLSA_STOP_NO_ZERO_ARM, arithmetic_flags, default_flags, get_engine
+from ._driver import (effective_weights, init_factors, init_refit_factors, resolve_flags, scoped_arithmetic,
+                      scoped_p_budget)
+from .engine import PLSA_FUSED, PLSA_SW_LL_ONLY, PLSA_STOP_NO_ZERO_ARM, arithmetic_flags, get_engine
 from .utils import (_check_sample_weight, coherence, log_lift, mean_coherence, mean_log_lift, normalize,
                     standardize_input)
 
@@ -66,45 +66,7 @@ def _locked(fn):
     return wrapper
 
 
-class _KernelArithmetic:
-    """Arithmetic of ONE kernel-level call on the shared engine (None = the engine's own or ENSTOP_AMD_ARITHMETIC;
-    "reference": the reference's bits, which presupposes the reference's entry order -- triplets that had to be re-sorted
-    are summed in row-major order); the engine is handed back in its default arithmetic."""
-
-    def __init__(self, eng, arithmetic):
-        self.eng = eng
-        self.arithmetic = arithmetic if arithmetic is not None else (os.environ.get("ENSTOP_AMD_ARITHMETIC") or None)
-
-    def __enter__(self):
-        self.eng.set_arithmetic(self.arithmetic)
-
-    def __exit__(self, *exc):
-        self.eng.set_arithmetic(None)
-
-
-class _PBudget:
-    """`p_budget=` of ONE fit / refit on the shared engine: bytes P(z|w,d) may take in the reference arithmetic
-    (Engine.set_p_budget: the documents are walked in blocks that fit, same bits).  None reads ENSTOP_AMD_P_BUDGET_MB
-    (unset: no budget).  No effect outside the reference arithmetic.  The engine gets its previous budget back."""
-
-    def __init__(self, eng, p_budget):
-        self.eng = eng
-        if p_budget is None:
-            mb = os.environ.get("ENSTOP_AMD_P_BUDGET_MB") or None
-            p_budget = None if mb is None else int(float(mb) * (1 << 20))
-        self.p_budget = p_budget
-
-    def __enter__(self):
-        self.before = getattr(self.eng, "p_budget", 0)
-        if self.p_budget is not None:
-            self.eng.set_p_budget(self.p_budget)
-
-    def __exit__(self, *exc):
-        if self.p_budget is not None:
-            self.eng.set_p_budget(self.before)
-
-
-def _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device=None, arithmetic=None):
+def _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device=None):
     k, m = p_w_given_z.shape
     n = p_z_given_d.shape[0]
     csr, order = _coo_to_csr(X_rows, X_cols, X_vals, n, m)
@@ -118,8 +80,8 @@ def _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device=None, arithm
 def plsa_e_step(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, p_z_given_wd,
                 probability_threshold=1e-32, device=None, arithmetic=None):
     """P(z|w,d) for every stored (d, w); fills and returns `p_z_given_wd` [nnz, k]."""
-    eng, order = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device, arithmetic)
-    with _KernelArithmetic(eng, arithmetic):
+    eng, order = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device)
+    with scoped_arithmetic(eng, arithmetic):
         P = eng.e_step(probability_threshold)
     if order is None:
         p_z_given_wd[...] = P
@@ -131,10 +93,10 @@ def plsa_e_step(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, p_z_given_wd,
 @_locked
 def _m_step(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, p_z_given_wd, sample_weight,
             norm_pwz, norm_pdz, update_v, device, arithmetic=None):
-    eng, order = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device, arithmetic)
+    eng, order = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device)
     P = np.asarray(p_z_given_wd, np.float32)
     eng.set_p(P if order is None else P[order])
-    with _KernelArithmetic(eng, arithmetic):
+    with scoped_arithmetic(eng, arithmetic):
         npwz, npdz = eng.m_step(sample_weight, update_v=update_v)
     U, V = eng.get_factors(want_v=update_v)
     p_z_given_d[...] = U
@@ -172,8 +134,8 @@ def plsa_refit_m_step(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, p_z_give
 @_locked
 def log_likelihood(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, sample_weight, device=None, arithmetic=None):
     """sum x * log(sum_z P(w|z) P(z|d)) * sample_weight[d], returned as float32 like the reference."""
-    eng, _ = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device, arithmetic)
-    with _KernelArithmetic(eng, arithmetic):
+    eng, _ = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device)
+    with scoped_arithmetic(eng, arithmetic):
         return np.float32(eng.log_likelihood(sample_weight))
 
 
@@ -243,15 +205,11 @@ def plsa_fit_inner(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, sample_weig
                    use_sample_weights=False, device=None, flags=None, arithmetic=None):
     """EM loop on COO triplets; factor arrays are updated in place and returned (plsa.py:517-640)."""
     eng, _ = _stage(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, device)
-    sw = np.asarray(sample_weight, np.float32)
-    flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
+    sw = effective_weights(np.asarray(sample_weight, np.float32))          # (cast first, then compared)
     # the weighted M-step only when requested (plsa.py:606-628); the log-likelihood always sees the
     # weights (plsa.py:591, 631): non-unit weights with use_sample_weights=False reach the engine
     # with the PLSA_SW_LL_ONLY flag
-    if not np.any(sw != 1.0):
-        sw = None
-    elif not use_sample_weights:
-        flags |= PLSA_SW_LL_ONLY
+    flags = resolve_flags(flags, arithmetic, 0 if sw is None or use_sample_weights else PLSA_SW_LL_ONLY)
     eng.fit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags)
     U, V = eng.get_factors()
     p_z_given_d[...] = U
@@ -262,45 +220,8 @@ def plsa_fit_inner(X_rows, X_cols, X_vals, p_w_given_z, p_z_given_d, sample_weig
 def _fit_on_engine(eng, k, sample_weight, init, n_iter, n_iter_per_test, tolerance, e_step_thresh,
                    random_state, flags=None, trace=False, shape=None, X_for_init=None):
     """plsa_fit's body for a corpus already resident on `eng` (shared with the ensemble member)."""
-    n, m, _ = eng.shape
-    rng = check_random_state(random_state)
-    if isinstance(init, str) and init == "device_random":
-        # additive, non-reference option: counter-based RNG on the GPU (host MT19937 draws cost
-        # ~1 s for 1M x 64 + 64 x 100k, four times the 50-iteration fit itself)
-        eng.init_factors_device(k, int(rng.randint(0, 2 ** 31 - 1)))
-        sw = None
-        if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
-            sw = np.asarray(sample_weight, np.float32)
-        return eng.fit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=trace)
-
-    device_init = os.environ.get("ENSTOP_AMD_HOST_INIT", "auto")   # "1": host, "0": device, auto: by size
-    use_device_init = device_init == "0" or (device_init == "auto" and k * (n + m) >= 262_144)
-    if isinstance(init, str) and init == "random" and isinstance(rng, np.random.RandomState) and use_device_init:
-        # same draws, same float64 normalisation, same float32 casts as plsa_init + plsa.py:709-710,
-        # evaluated on the device from rng's own MT19937 state (bit-identical, rng is advanced).  Long
-        # streams are cut into jump-ahead pieces (csrc/mt_jump.hpp): config 3's 141 M words take 8 ms
-        # against 0.45 s for the host draws + normalisation + upload; tiny problems stay on the host
-        eng.init_factors_numpy_stream(k, rng)
-        sw = None
-        if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
-            sw = np.asarray(sample_weight, np.float32)
-        return eng.fit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=trace)
-
-    class _Shape:                      # plsa_init only needs .shape for "random" / tuple inits
-        pass
-    Xs = X_for_init
-    if Xs is None:
-        Xs = _Shape()
-        Xs.shape = (n, m)
-    p_z_given_d, p_w_given_z = plsa_init(Xs, k, init=init, rng=rng)
-    p_z_given_d = p_z_given_d.astype(np.float32, order="C")
-    p_w_given_z = p_w_given_z.astype(np.float32, order="C")
-    sw = None
-    if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):   # plsa.py:712
-        sw = np.asarray(sample_weight, np.float32)
-    eng.set_factors(p_z_given_d, p_w_given_z)
-    iters, ll = eng.fit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=trace)
-    return iters, ll
+    init_factors(eng, k, init, check_random_state(random_state), X_for_init)
+    return eng.fit(effective_weights(sample_weight), n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=trace)
 
 
 @_locked
@@ -317,11 +238,9 @@ def plsa_fit(X, k, sample_weight, init="random", n_iter=100, n_iter_per_test=10,
         X = csr_matrix(X)
     eng = get_engine(device)
     eng.upload_csr(X)
-    if arithmetic is not None:
-        flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
-    with _PBudget(eng, p_budget):
-        iters, ll = _fit_on_engine(eng, k, sample_weight, init, n_iter, n_iter_per_test, tolerance,
-                                   e_step_thresh, random_state, flags, trace=return_info, X_for_init=X)
+    with scoped_p_budget(eng, p_budget):
+        iters, ll = _fit_on_engine(eng, k, sample_weight, init, n_iter, n_iter_per_test, tolerance, e_step_thresh,
+                                   random_state, resolve_flags(flags, arithmetic), trace=return_info, X_for_init=X)
     p_z_given_d, p_w_given_z = eng.get_factors()
     if return_info:
         return p_z_given_d, p_w_given_z, dict(n_iter=iters, log_likelihood_trace=ll)
@@ -333,10 +252,8 @@ def plsa_refit_inner(X_rows, X_cols, X_vals, topics, p_z_given_d, sample_weight,
                      n_iter_per_test=10, tolerance=0.005, e_step_thresh=1e-32, device=None, flags=None, arithmetic=None):
     """EM on P(z|d) with the topics frozen (plsa.py:820-920); returns P(z|d)."""
     eng, _ = _stage(X_rows, X_cols, X_vals, topics, p_z_given_d, device)
-    sw = np.asarray(sample_weight, np.float32)
-    if arithmetic is not None:
-        flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
-    eng.refit(None if not np.any(sw != 1.0) else sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags)
+    sw = effective_weights(np.asarray(sample_weight, np.float32))          # (cast first, then compared)
+    eng.refit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, resolve_flags(flags, arithmetic))
     U, _ = eng.get_factors(want_v=False)
     p_z_given_d[...] = U
     return p_z_given_d
@@ -348,13 +265,12 @@ def plsa_refit(X, topics, sample_weight, n_iter=50, n_iter_per_test=10, toleranc
                p_budget=None):
     """Document vectors P(z|d) for X against fixed `topics` (plsa.py:923-997).  p_budget: as in plsa_fit (bytes for
     P(z|w,d) in the reference arithmetic; no effect outside it)."""
-    if arithmetic is not None:
-        flags = (default_flags() if flags is None else flags) | arithmetic_flags(arithmetic)
     if not issparse(X):
         X = csr_matrix(X)
     eng = get_engine(device)
     iters, ll = _refit_on_engine(eng, X, topics, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh,
-                                 check_random_state(random_state), flags, trace=return_info, p_budget=p_budget)
+                                 check_random_state(random_state), resolve_flags(flags, arithmetic), trace=return_info,
+                                 p_budget=p_budget)
     U, _ = eng.get_factors(want_v=False)
     if return_info:
         return U, dict(n_iter=iters, log_likelihood_trace=ll)
@@ -365,25 +281,11 @@ def _refit_on_engine(eng, X, topics, sample_weight, n_iter, n_iter_per_test, tol
                      trace=False, p_budget=None):
     """plsa_refit's body on `eng`, whose lock the caller holds: X becomes the resident corpus, P(z|d) is drawn from `rng`
     and folded in against the fixed `topics`, and both stay on the device (scoring.held_out_scores goes on from there)."""
-    topics = np.asarray(topics)
-    k = topics.shape[0]
     eng.upload_csr(X)
-    device_init = os.environ.get("ENSTOP_AMD_HOST_INIT", "auto")
-    if isinstance(rng, np.random.RandomState) and (
-            device_init == "0" or (device_init == "auto" and k * X.shape[0] >= 262_144)):
-        # rng.rand(n, k), float64 row normalisation, float32 cast (plsa.py:979-981) on the device
-        # from rng's own stream: bit-identical, 0.22 s of host draws saved at 1 M documents x 64
-        eng.init_factors_numpy_stream(k, rng, topics=topics)
-    else:
-        p_z_given_d = rng.rand(X.shape[0], k)                # plsa.py:979
-        normalize(p_z_given_d, axis=1)
-        p_z_given_d = p_z_given_d.astype(np.float32)
-        eng.set_factors(p_z_given_d, topics.astype(np.float32))
-    sw = None
-    if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
-        sw = np.asarray(sample_weight, np.float32)
-    with _PBudget(eng, p_budget):
-        return eng.refit(sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=trace)
+    init_refit_factors(eng, X.shape[0], topics, rng)
+    with scoped_p_budget(eng, p_budget):
+        return eng.refit(effective_weights(sample_weight), n_iter, n_iter_per_test, tolerance, e_step_thresh, flags,
+                         trace=trace)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -412,6 +314,19 @@ class _ScoringMixin:
     """score_samples() / score() / perplexity() of a fitted model on documents X (scoring.held_out_scores), what
     scikit-learn's own topic model offers.  The fold-in uses the estimator's `components_`, `transform_random_seed`,
     flags and `device`, and transform's fixed n_iter=50, n_iter_per_test=5, tolerance=0.001."""
+
+    def _transform(self, X, sample_weight=None):
+        """transform() of the estimators: the fold-in of X against `components_` under unit (or the given) weights"""
+        X = check_array(X, accept_sparse="csr")
+        sample_weight = _check_sample_weight(sample_weight, X, dtype=np.float32)
+        random_state = check_random_state(self.transform_random_seed)
+        # the reference converts to COO here (plsa.py:1208); the engine consumes the CSR arrays in the
+        # same entry order directly (and, unlike a COO -> CSR round trip, never merges duplicates)
+        X = csr_matrix(X) if not issparse(X) else X.tocsr()
+        # plsa.py:1210-1218: fixed n_iter=50, n_iter_per_test=5, tolerance=0.001
+        return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5, tolerance=0.001,
+                          random_state=random_state, device=self.device,
+                          flags=self._flags() if hasattr(self, "_flags") else None, p_budget=getattr(self, "p_budget", None))
 
     def _held_out(self, X, method, fraction=0.5, on_zero="inf"):
         from .scoring import held_out_scores
@@ -477,11 +392,12 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
         self.device = device
 
     _extra_flags = 0      # subclasses: stop-test variant of the reference module they stand in for
+    _base_flags = None    # None: default_flags(), the environment consulted (StreamedPLSA: its own base)
     tempering = None      # (class default: estimators unpickled from before the parameter existed, and the subclasses)
 
     def _flags(self):
         # arithmetic="reference": the reference's float32 sums, rounding for rounding (engine.arithmetic_flags)
-        return default_flags() | self._extra_flags | arithmetic_flags(getattr(self, "arithmetic", None))
+        return resolve_flags(None, getattr(self, "arithmetic", None), self._extra_flags, self._base_flags)
 
     # `tempering` is listed among the parameters only while it is set: the parameter lists of existing pipelines, grids and
     # pickles are what they were, and clone() still carries a value that was given
@@ -558,16 +474,7 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
         return self.embedding_
 
     def transform(self, X, y=None):
-        X = check_array(X, accept_sparse="csr")
-        random_state = check_random_state(self.transform_random_seed)
-        sample_weight = _check_sample_weight(None, X, dtype=np.float32)
-        # the reference converts to COO here (plsa.py:1208); the engine consumes the CSR arrays in the
-        # same entry order directly (and, unlike a COO -> CSR round trip, never merges duplicates)
-        X = csr_matrix(X) if not issparse(X) else X.tocsr()
-        # plsa.py:1210-1218: fixed n_iter=50, n_iter_per_test=5, tolerance=0.001
-        return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5,
-                          tolerance=0.001, random_state=random_state, device=self.device,
-                          flags=self._flags(), p_budget=getattr(self, "p_budget", None))
+        return self._transform(X, None)
 
 
 class StreamedPLSA(PLSA):
@@ -587,21 +494,12 @@ class StreamedPLSA(PLSA):
 
     # streamed_plsa.py:596-597: the stop test has no `change == 0` arm
     _extra_flags = PLSA_STOP_NO_ZERO_ARM
-
-    def _flags(self):
-        from .engine import PLSA_FUSED
-        return PLSA_FUSED | self._extra_flags | arithmetic_flags(getattr(self, "arithmetic", None))
+    _base_flags = PLSA_FUSED      # the environment is not consulted (resolve_flags says why)
 
     def transform(self, X, y=None, sample_weight=None):
         """streamed_plsa.py:1237: unlike PLSA.transform this one takes `sample_weight` (it only enters
         the log-likelihood of plsa_refit, whose stop test never fires: same vectors either way)."""
-        X = check_array(X, accept_sparse="csr")
-        sample_weight = _check_sample_weight(sample_weight, X, dtype=np.float32)
-        random_state = check_random_state(self.transform_random_seed)
-        X = csr_matrix(X) if not issparse(X) else X.tocsr()
-        return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5,
-                          tolerance=0.001, random_state=random_state, device=self.device,
-                          flags=self._flags(), p_budget=getattr(self, "p_budget", None))
+        return self._transform(X, sample_weight)
 
 
 class BlockParallelPLSA(PLSA):

@@ -23,8 +23,8 @@ import os
 import numpy as np
 from sklearn.utils import check_random_state
 
+from ._driver import effective_weights, host_factors, resolve_flags
 from .engine import Engine
-from .plsa import plsa_init
 
 
 def row_ranges_by_nnz(indptr, parts):
@@ -144,11 +144,8 @@ def sharded_plsa_fit(X, k, sample_weight=None, init="random", n_iter=100, n_iter
     X = X.tocsr()
     n, m = X.shape
     rng = check_random_state(random_state)
-    U0, V0 = plsa_init(X, k, init=init, rng=rng)                    # global stream, sliced per shard
-    U0 = U0.astype(np.float32, order="C"); V0 = V0.astype(np.float32, order="C")
-    sw_all = None
-    if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
-        sw_all = np.asarray(sample_weight, np.float32)
+    U0, V0 = host_factors(k, init, rng, X=X)                        # global stream, sliced per shard
+    sw_all = effective_weights(sample_weight)
 
     native = on_comm_engine = False
     if local_shards:
@@ -190,7 +187,7 @@ def sharded_plsa_fit(X, k, sample_weight=None, init="random", n_iter=100, n_iter
                 if i != lender:
                     e.p_borrow(shared, max(need))
         if native:
-            fl = (PLSA_FUSED if flags is None else flags) | PLSA_SHARDED | (0 if zero_arm else PLSA_STOP_NO_ZERO_ARM)
+            fl = resolve_flags(flags, extra=PLSA_SHARDED | (0 if zero_arm else PLSA_STOP_NO_ZERO_ARM), base=PLSA_FUSED)
             iters, trace = engines[0].fit(sws[0], n_iter, n_iter_per_test, tolerance, e_step_thresh, fl,
                                           trace=return_info)
         else:

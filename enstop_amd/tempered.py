@@ -21,8 +21,9 @@ import numpy as np
 from scipy.sparse import csr_matrix, issparse
 from sklearn.utils import check_random_state
 
-from .engine import PLSA_FUSED, PLSA_STOP_NO_ZERO_ARM, default_flags, get_engine
-from .plsa import _fit_on_engine, _locked, _refit_on_engine
+from ._driver import effective_weights, init_factors, resolve_flags
+from .engine import PLSA_FUSED, PLSA_STOP_NO_ZERO_ARM, get_engine
+from .plsa import _locked, _refit_on_engine
 from .scoring import _nonempty_rows, split_documents
 
 SNAPSHOT, RESTORE, BURST, STOP = "snapshot", "restore", "burst", "stop"
@@ -152,7 +153,7 @@ def plsa_fit_tempered(X, k, sample_weight=None, init="random", validation_fracti
     before the schedule's answer is carried out: the engine then holds that burst's factors and the observed corpus."""
     if not 0.0 < validation_fraction < 1.0:
         raise ValueError("validation_fraction must be in (0, 1), not %r" % (validation_fraction,))
-    flags = (default_flags() if flags is None else int(flags)) | PLSA_STOP_NO_ZERO_ARM
+    flags = resolve_flags(flags, extra=PLSA_STOP_NO_ZERO_ARM)
     if not flags & PLSA_FUSED:
         raise ValueError("tempered EM runs the fused schedule only (ENSTOP_AMD_MATERIALISE / flags without PLSA_FUSED)")
     X = X.tocsr() if issparse(X) else csr_matrix(X)
@@ -160,14 +161,12 @@ def plsa_fit_tempered(X, k, sample_weight=None, init="random", validation_fracti
     schedule = TemperingSchedule(eta, beta_min, rel_tol, n_iter_per_test, n_iter)
     observed, held = split_documents(X, 1.0 - validation_fraction, rng)
     scored = _nonempty_rows(observed) & _nonempty_rows(held)
-    sw = None
-    if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
-        sw = np.asarray(sample_weight, np.float32)
+    sw = effective_weights(sample_weight)
     eng = get_engine(device)
     eng.upload_csr(observed)
-    # the initialisation of plsa_fit, and the likelihood of the starting factors; no iteration
-    _, ll0 = _fit_on_engine(eng, k, sample_weight, init, 0, n_iter_per_test, 0.0, e_step_thresh, rng, flags, trace=True,
-                            X_for_init=observed)
+    # the initialisation of plsa_fit, and the likelihood of the starting factors: a traced fit of no iteration
+    init_factors(eng, k, init, rng, observed)
+    _, ll0 = eng.fit(sw, 0, n_iter_per_test, 0.0, e_step_thresh, flags, trace=True)
     report = dict(betas=[], iterations=[], perplexities=[], training_log_likelihoods=[], unscored_shares=[], improved=[],
                   actions=[], initial_training_log_likelihood=float(ll0[0]) if len(ll0) else None, selected_beta=None,
                   selected_iteration=0, selected_perplexity=None, unscored_share=0.0, n_iter=0,
@@ -213,16 +212,14 @@ def plsa_fit_fixed_beta(X, k, beta, sample_weight=None, init="random", n_iter=10
     likelihood stops the fit as usual.  -> (P(z|d), P(w|z), dict(n_iter, log_likelihood_trace))."""
     if not 0.0 < float(beta) <= 1.0:
         raise ValueError("beta must be in (0, 1], not %r" % (beta,))
-    flags = default_flags() if flags is None else int(flags)
+    flags = resolve_flags(flags)
     if not flags & PLSA_FUSED:
         raise ValueError("tempered EM runs the fused schedule only (ENSTOP_AMD_MATERIALISE / flags without PLSA_FUSED)")
     X = X.tocsr() if issparse(X) else csr_matrix(X)
-    sw = None
-    if sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0):
-        sw = np.asarray(sample_weight, np.float32)
     eng = get_engine(device)
     eng.upload_csr(X)
-    _fit_on_engine(eng, k, sample_weight, init, 0, n_iter_per_test, 0.0, e_step_thresh, random_state, flags, X_for_init=X)
-    iters, ll = eng.fit_tempered(float(beta), sw, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace=True)
+    init_factors(eng, k, init, check_random_state(random_state), X)
+    iters, ll = eng.fit_tempered(float(beta), effective_weights(sample_weight), n_iter, n_iter_per_test, tolerance,
+                                 e_step_thresh, flags, trace=True)
     U, V = eng.get_factors()
     return U, V, dict(n_iter=iters, log_likelihood_trace=ll)

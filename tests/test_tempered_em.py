@@ -321,6 +321,31 @@ def test_the_loop_is_the_step_iterated(amd, k):
         eng.close()
 
 
+@pytest.mark.gpu
+def test_fixed_beta_fit_is_the_initialisation_followed_by_the_tempered_loop(amd):
+    """plsa_fit_fixed_beta puts plsa_fit's starting factors on the device (_driver.init_factors) and runs fit_tempered: no
+    zero-iteration fit stands between the two, and none is missed -- the same two calls on an engine of one's own give the
+    same bits."""
+    from enstop_amd._driver import init_factors
+    from enstop_amd.engine import default_flags
+    from enstop_amd.tempered import plsa_fit_fixed_beta
+    rs = np.random.RandomState(5)
+    dense = np.ceil(rs.rand(6, 9) * 4) * (rs.rand(6, 9) < 0.3)
+    dense[np.arange(9) % 6, np.arange(9)] += 1.0                   # no empty document, no empty word
+    X = sp.csr_matrix(dense.astype(np.float32))
+    assert X.shape == (6, 9) and 15 <= X.nnz <= 25
+    seed = 11
+    U, V, info = plsa_fit_fixed_beta(X, 3, 0.8, random_state=seed, n_iter=4, n_iter_per_test=2)
+    with make_engine(amd, {}, X) as eng:
+        init_factors(eng, 3, "random", np.random.RandomState(seed), X)
+        iters, trace = eng.fit_tempered(0.8, None, 4, 2, 0.001, 1e-32, default_flags(), trace=True)
+        Ue, Ve = eng.get_factors()
+    assert info["n_iter"] == iters and iters >= 1
+    same_bits(info["log_likelihood_trace"], trace, "trace")
+    same_bits(U, Ue, "U")
+    same_bits(V, Ve, "V")
+
+
 # ------------------------------------------------------------------------------------------------
 # G. snapshot / restore
 # ------------------------------------------------------------------------------------------------
