@@ -1,5 +1,6 @@
 """ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h,
-plsa_hip_metrics.h, plsa_hip_blocked.h, plsa_hip_embed.h, plsa_hip_nmf.h, plsa_hip_score.h and plsa_hip_tempered.h).
+plsa_hip_metrics.h, plsa_hip_blocked.h, plsa_hip_embed.h, plsa_hip_nmf.h, plsa_hip_score.h, plsa_hip_tempered.h and
+plsa_hip_online.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -166,6 +167,19 @@ TEMPERED_SIGNATURES = {
     "plsa_factors_restore": (C.c_int, [_ctx]),
 }
 
+# include/plsa_hip_online.h: online (stepwise) EM on a state that outlives its block contexts (its own table as well)
+_online = C.c_void_p
+ONLINE_SIGNATURES = {
+    "plsa_online_create": (C.c_int, [_ctx, _i64, _i32, C.POINTER(_online)]),
+    "plsa_online_destroy": (None, [_online]),
+    "plsa_online_set_topics": (C.c_int, [_online, _f32p]),
+    "plsa_online_get_topics": (C.c_int, [_online, _f32p]),
+    "plsa_online_statistic_get": (C.c_int, [_online, _vp, C.POINTER(_i64)]),
+    "plsa_online_statistic_set": (C.c_int, [_online, _f32p]),
+    "plsa_online_step": (C.c_int, [_online, _ctx, _vp, _i32, C.c_float, C.c_double, C.c_double, _i32, C.POINTER(C.c_double)]),
+    "plsa_online_fold": (C.c_int, [_online, _ctx, _vp, _i32, C.c_float, _i32]),
+}
+
 _lib = None
 HW_QUEUES ={"set_by": None, "hip_mapped_before_load": None}
 
@@ -217,7 +231,7 @@ def load():
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
             list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + \
-            list(TEMPERED_SIGNATURES.items()):
+            list(TEMPERED_SIGNATURES.items()) + list(ONLINE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -38,6 +38,7 @@
 #include "../../include/plsa_hip_nmf.h"
 #include "../../include/plsa_hip_score.h"
 #include "../../include/plsa_hip_tempered.h"
+#include "../../include/plsa_hip_online.h"
 #include "mt_jump.hpp"
 #include "plsa_embed_kernels.hpp"
 #include "plsa_init_kernels.hpp"
@@ -2284,3 +2285,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_score.hpp"           // ... and its host side
 #include "plsa_tempered_kernels.hpp"   // tempered EM (include/plsa_hip_tempered.h): the power of a factor table ...
 #include "plsa_tempered.hpp"           // ... and the loop, the snapshot slot and the diagnostic read-back
+#include "plsa_online_kernels.hpp"     // online (stepwise) EM (include/plsa_hip_online.h): the blend of the statistic ...
+#include "plsa_online.hpp"             // ... and the state, the step and the fold

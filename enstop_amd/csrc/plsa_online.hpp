@@ -1,0 +1,248 @@
+// plsa_online.hpp -- host side of online (stepwise) EM (include/plsa_hip_online.h); part of plsa_hip.hip's translation unit
+// (included at its end: it uses the context, the pass wrappers and the normalisation kernels).
+//
+// A plsa_online state owns the topics V [m, kp], the running statistic S [m, kp], the slab sums and the norm of the global
+// update, a step counter and ONE event.  A step runs on the block context's one stream: the state's V is swapped into the place
+// the block's passes read (c->Vt[c->cv], as TemperedInputs does it) for the length of the pass chain, then the blend, the
+// norm and the division follow on the same stream.  Steps on different contexts are ordered on the device by the event:
+// waited for by the stream at the start of a step or fold, recorded at its end.  No second stream, no look-ahead, no hipGraph.
+#pragma once
+
+struct plsa_online {
+    plsa_ctx *home = nullptr;        // its device, its stream and staging buffer for the host <-> device copies of V and S
+    int device = 0;
+    i64 m = 0;
+    int k = 0, kp = 0;
+    DevBuf S, V, slabs, norm;
+    Event ev;
+    bool recorded = false;           // ev has been recorded at least once
+    int64_t t = 0;                   // steps taken since plsa_online_set_topics
+};
+
+namespace {
+
+// the state's V in the place the block's passes read, for the length of one launch chain (the launches are stream-ordered:
+// the pointers they were given stay valid, the buffers only change names on the host)
+struct OnlineTopics {
+    plsa_ctx *c;
+    plsa_online *st;
+    OnlineTopics(plsa_online *st_, plsa_ctx *c_) : c(c_), st(st_) { swap(); }
+    ~OnlineTopics() { swap(); }
+    void swap() { c->Vt[c->cv].swap(st->V); }
+};
+
+size_t online_table_bytes(const plsa_online *st) { return sizeof(float) * (size_t)st->m * st->kp; }
+
+// every refusal of a step or fold that looks at the state and the block context only; launches nothing
+int online_eligible(plsa_online *st, plsa_ctx *c, const char *who, int flags) {
+    if (!st) return fail(c, "%s: no state", who);
+    if (!(flags & PLSA_FUSED)) return fail(c, "%s: online EM runs the fused passes only (flags without PLSA_FUSED)", who);
+    if (flags & (PLSA_SHARDED | PLSA_GRAPH | PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL))
+        return fail(c, "%s: PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS and PLSA_REFERENCE_LL have no online form (flags=%d)", who, flags);
+    if (c->ref_sums || c->ref_ll) return fail(c, "%s: the context is in reference arithmetic (plsa_set_arithmetic), which has no online form", who);
+    if (c->sharded || c->comm) return fail(c, "%s: the context is one shard of a communicator; online EM has no doc-sharded form", who);
+    if (c->device != st->device) return fail(c, "%s: the state lives on device %d, the block context on device %d", who, st->device, c->device);
+    CHK(need_factors(c));
+    if (c->m != st->m || c->k != st->k || c->kp != st->kp)
+        return fail(c, "%s: the state holds topics for %lld words with k=%d, the block context has %lld words with k=%d", who,
+                    (long long)st->m, st->k, (long long)c->m, c->k);
+    if (c->Vt[c->cv].cap < online_table_bytes(st)) return fail(c, "internal: %s: the block's topic table is smaller than the state's", who);
+    return 0;
+}
+
+// what another context's step or fold enqueued precedes what this one enqueues
+int online_wait(plsa_online *st, plsa_ctx *c) {
+    if (st->recorded) HIPCHK(c, hipStreamWaitEvent(c->stream, st->ev, 0));
+    return 0;
+}
+int online_record(plsa_online *st, plsa_ctx *c) {
+    HIPCHK(c, hipEventRecord(st->ev, c->stream));
+    st->recorded = true;
+    return 0;
+}
+// the host waits for the last step or fold (before it reads or writes the state's tables through the home stream)
+int online_host_wait(plsa_online *st) {
+    plsa_ctx *h = st->home;
+    HIPCHK(h, hipSetDevice(st->device));
+    if (st->recorded) HIPCHK(h, hipEventSynchronize(st->ev));
+    return 0;
+}
+
+// frozen-topic iterations: the document pass of the fused refit, P(z|d) of the block only
+int online_fold_in(plsa_ctx *c, int n_iter, const float *d_sw, float thresh) {
+    for (int i = 0; i < n_iter; ++i) {
+        CHK(run_row_pass(c, false, false, d_sw, thresh, nullptr, nullptr));
+        c->cu ^= 1;
+    }
+    return 0;
+}
+
+// S' = b Vacc + a S with its slab sums, norm, V' = S' / norm: three launches on the block's stream
+int online_global_update(plsa_online *st, plsa_ctx *c, float a, float b) {
+    const int nb = plsa::plan::blend_grid(st->m);
+    {
+        Scope s(c, "k_online_blend");
+        hipLaunchKernelGGL(plsa::k_online_blend, dim3(nb), dim3(plsa::plan::BLEND_BLOCK), 0, c->stream, st->S.as<float4>(),
+                           c->Vacc.as<float4>(), (long long)st->m, st->kp, a, b, st->slabs.as<double>());
+    }
+    {
+        Scope s(c, "k_colsum_final");
+        hipLaunchKernelGGL(plsa::k_colsum_final, dim3(1), dim3(256), 0, c->stream, st->slabs.as<double>(), nb, st->kp,
+                           st->norm.as<float>());
+    }
+    {
+        Scope s(c, "k_v_normalise");
+        const i64 total4 = st->m * st->kp / 4;
+        hipLaunchKernelGGL(plsa::k_v_normalise, dim3(grid_for(c, total4, 256)), dim3(256), st->kp * sizeof(float), c->stream,
+                           st->S.as<float>(), st->V.as<float>(), (int)st->m, st->kp, st->norm.as<float>());
+    }
+    return launch_check(c, "k_online_blend");
+}
+
+// host [k, m] -> one of the state's tables [m, kp] (scale: every entry divided by it first, in float32), through the home
+// context's staging buffer and stream; synchronous
+int online_upload(plsa_online *st, const float *host, DevBuf &table, float divide_by) {
+    plsa_ctx *h = st->home;
+    const size_t count = (size_t)st->k * st->m;
+    std::vector<float> scaled;
+    if (divide_by != 1.0f) {
+        scaled.resize(count);
+        for (size_t i = 0; i < count; ++i) scaled[i] = host[i] / divide_by;
+        host = scaled.data();
+    }
+    CHK(ensure(h, h->tmp0, sizeof(float) * count));
+    HIPCHK(h, hipMemcpyAsync(h->tmp0.p, host, sizeof(float) * count, hipMemcpyHostToDevice, h->stream));
+    const iplan::Grid2 g = iplan::transpose_grid(st->m, st->kp);
+    hipLaunchKernelGGL(plsa::k_v_to_vt, dim3(g.x, g.y), dim3(256), 0, h->stream, h->tmp0.as<float>(), table.as<float>(), st->k,
+                       (int)st->m, st->kp);
+    CHK(launch_check(h, "k_v_to_vt"));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int online_download(plsa_online *st, const DevBuf &table, float *host) {
+    plsa_ctx *h = st->home;
+    const size_t count = (size_t)st->k * st->m;
+    CHK(ensure(h, h->tmp0, sizeof(float) * count));
+    const iplan::Grid2 g = iplan::transpose_grid(st->m, st->kp);
+    hipLaunchKernelGGL(plsa::k_vt_to_v, dim3(g.x, g.y), dim3(256), 0, h->stream, table.as<float>(), h->tmp0.as<float>(), st->k,
+                       (int)st->m, st->kp);
+    CHK(launch_check(h, "k_vt_to_v"));
+    CHK(copy_to_host(h, host, h->tmp0.p, sizeof(float) * count));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int plsa_online_create(plsa_ctx *home, int64_t m, int32_t k, plsa_online **out) {
+    if (!out) return fail(home, "plsa_online_create: out is NULL");
+    *out = nullptr;
+    if (!home) return fail(nullptr, "plsa_online_create: no home context");
+    HIPCHK(home, hipSetDevice(home->device));
+    if (k <= 0 || k > 1024) return fail(home, "plsa_online_create: k=%d outside [1,1024]", k);
+    if (m <= 0 || m >= ((int64_t)1 << 31) - 1) return fail(home, "plsa_online_create: m=%lld outside [1, 2^31 - 2]", (long long)m);
+    std::unique_ptr<plsa_online> owner(new plsa_online());
+    plsa_online *st = owner.get();
+    st->home = home; st->device = home->device; st->m = m; st->k = k;
+    st->kp = plsa::plan::lane_shape(k, home->chunks_per_lane, home->row_shape_8x2).kp;
+    static_assert(plsa::plan::BLEND_MAX_KP >= 1024, "k <= 1024");
+    const size_t bytes = online_table_bytes(st);
+    CHK(ensure(home, st->S, bytes));
+    CHK(ensure(home, st->V, bytes));
+    CHK(ensure(home, st->slabs, sizeof(double) * (size_t)plsa::plan::blend_grid(m) * st->kp));
+    CHK(ensure(home, st->norm, sizeof(float) * (size_t)st->kp));
+    HIPCHK(home, hipMemsetAsync(st->S.p, 0, bytes, home->stream));
+    HIPCHK(home, hipMemsetAsync(st->V.p, 0, bytes, home->stream));
+    HIPCHK(home, hipStreamSynchronize(home->stream));
+    HIPCHK(home, hipEventCreateWithFlags(&st->ev.h, hipEventDisableTiming));
+    *out = owner.release();
+    return 0;
+}
+
+void plsa_online_destroy(plsa_online *st) {
+    if (!st) return;
+    (void)hipSetDevice(st->device);
+    if (st->recorded) (void)hipEventSynchronize(st->ev);
+    delete st;
+}
+
+int plsa_online_set_topics(plsa_online *st, const float *V) {
+    if (!st) return fail(nullptr, "plsa_online_set_topics: no state");
+    if (!V) return fail(st->home, "plsa_online_set_topics: V is NULL");
+    CHK(online_host_wait(st));
+    CHK(online_upload(st, V, st->V, 1.0f));
+    CHK(online_upload(st, V, st->S, (float)st->k));
+    st->t = 0;
+    return 0;
+}
+
+int plsa_online_get_topics(plsa_online *st, float *V) {
+    if (!st) return fail(nullptr, "plsa_online_get_topics: no state");
+    if (!V) return fail(st->home, "plsa_online_get_topics: V is NULL");
+    CHK(online_host_wait(st));
+    return online_download(st, st->V, V);
+}
+
+int plsa_online_statistic_get(plsa_online *st, float *S, int64_t *steps) {
+    if (!st) return fail(nullptr, "plsa_online_statistic_get: no state");
+    CHK(online_host_wait(st));
+    if (steps) *steps = st->t;
+    return S ? online_download(st, st->S, S) : 0;
+}
+
+int plsa_online_statistic_set(plsa_online *st, const float *S) {
+    if (!st) return fail(nullptr, "plsa_online_statistic_set: no state");
+    if (!S) return fail(st->home, "plsa_online_statistic_set: S is NULL");
+    CHK(online_host_wait(st));
+    return online_upload(st, S, st->S, 1.0f);
+}
+
+int plsa_online_step(plsa_online *st, plsa_ctx *c, const float *sw, int32_t inner_iter, float thresh, double rho, double scale,
+                     int32_t flags, double *ll_partial) {
+    if (!c) return fail(nullptr, "plsa_online_step: no block context");
+    CHK(online_eligible(st, c, "plsa_online_step", flags));
+    if (!(rho > 0.0 && rho <= 1.0)) return fail(c, "plsa_online_step: rho=%g outside (0, 1]", rho);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(c, "plsa_online_step: scale=%g is not a positive number", scale);
+    if (inner_iter < 0) return fail(c, "plsa_online_step: inner_iter=%d is negative", inner_iter);
+    const float a = (float)(1.0 - rho), b = (float)(rho * scale);
+    HIPCHK(c, hipSetDevice(c->device));
+    const float *d_sw = nullptr;
+    CHK(upload_sw(c, sw, &d_sw));
+    CHK(online_wait(st, c));
+    int blocks = 0;
+    {
+        OnlineTopics topics(st, c);
+        CHK(online_fold_in(c, inner_iter, d_sw, thresh));
+        CHK(run_row_pass(c, false, ll_partial != nullptr, d_sw, thresh, nullptr, &blocks));
+        CHK(run_col_pass(c, false, d_sw, thresh));
+    }
+    c->cu ^= 1;
+    c->p_state.invalidate();
+    if (ll_partial) CHK(finish_ll(c, blocks, nullptr));      // the scalar travels while the update runs
+    CHK(online_global_update(st, c, a, b));
+    CHK(online_record(st, c));
+    st->t += 1;
+    if (ll_partial) CHK(wait_ll(c, ll_partial));              // the only host wait of a step
+    return 0;
+}
+
+int plsa_online_fold(plsa_online *st, plsa_ctx *c, const float *sw, int32_t n_iter, float thresh, int32_t flags) {
+    if (!c) return fail(nullptr, "plsa_online_fold: no block context");
+    CHK(online_eligible(st, c, "plsa_online_fold", flags));
+    if (n_iter < 0) return fail(c, "plsa_online_fold: n_iter=%d is negative", n_iter);
+    HIPCHK(c, hipSetDevice(c->device));
+    const float *d_sw = nullptr;
+    CHK(upload_sw(c, sw, &d_sw));
+    CHK(online_wait(st, c));
+    {
+        OnlineTopics topics(st, c);
+        CHK(online_fold_in(c, n_iter, d_sw, thresh));
+    }
+    if (n_iter > 0) c->p_state.invalidate();
+    return online_record(st, c);       // a later step writes the topics this fold reads
+}
+
+}  // extern "C"
