@@ -161,12 +161,18 @@ struct plsa_ctx {
     int struct_row_lpn = 0;          // document-pass lane count the row items were sized for (struct_lpn: the column pass')
     DevBuf partial;
     bool use_item_order = true, xcd_split = true;
-    // packed entry streams of the fused passes (plsa_kernels.hpp: Packed): pk_csr parallel to col / val, pk_csc parallel to
-    // csc.row / csc.val.  A stream is used (ok) when its ids fit 24 bits and at most 1/16 of the entries escape.
+    // packed entry streams of the fused passes (plsa_kernels.hpp: Packed) in the line layout (plsa_launch_plan.hpp): pk_csr
+    // holds the documents (or, in row-item mode, the row items) of col / val in blocks of 4 * row_lpn words, pk_csc the column
+    // items of csc.row / csc.val in blocks of 4 * lpn words.  A stream is used (ok) when its ids fit 24 bits, at most 1/16
+    // of the entries escape and its words fit 32-bit offsets.
     bool packed = true;              // PLSA_PACKED=0: the two-array streams everywhere (A/B)
     struct PackedStream : Derived<PackedStream> {
         DevBuf buf;
+        DevBuf blk;                  // pk_csr over whole documents: n + 1 block offsets
+        int lpn = 0, seg = 0;        // what the layout was written for: lane count; item length (0: whole documents)
+        i64 words = 0;
         bool ok = false;
+        bool reshape = false;        // pk_csc: invalidated by a lane-shape change that kept the CSC copy (ensure_csc writes it again)
         int state() const { return !valid ? -1 : (ok ? 1 : 0); }   // -1 not built, 0 the pass runs on the arrays, 1 packed
     } pk_csr, pk_csc;
     DevBuf pk_count;
@@ -821,6 +827,7 @@ struct RowLaunch {
     bool items, packed, xcd_rows;    // over row items / the packed entry stream / PLSA_ROW_XCD's schedule
     const int *indptr, *colidx;      // colidx: the packed CSR stream when `packed`
     const float *vals;
+    const int *sblk;                 // `packed` over whole documents: their block offsets in the stream
     const int *order;                // visiting order of whole documents (nullptr over items, or unsorted)
     const int *ritem_row, *ritem_start, *ritem_first;   // nullptr on whole documents
     float *rpartial;                 // one k-vector per row item (nullptr on whole documents)
@@ -843,6 +850,7 @@ int prepare_row_pass(plsa_ctx *c, bool from_p, bool want_ll, RowLaunch &r) {
     if (!from_p) CHK(ensure_packed_csr(c));
     r.packed = !from_p && c->packed && c->pk_csr.ok;
     r.indptr = c->indptr; r.colidx = r.packed ? c->pk_csr.buf.as<int>() : c->col; r.vals = c->val;
+    r.sblk = r.packed && !r.items ? c->pk_csr.blk.as<int>() : nullptr;
     r.ritem_row = r.items ? c->ritems.row.as<int>() : nullptr;
     r.ritem_start = r.items ? c->ritems.start.as<int>() : nullptr;
     r.ritem_first = r.items ? c->ritems.first.as<int>() : nullptr;
@@ -865,7 +873,8 @@ int run_row_pass(plsa_ctx *c, bool from_p, bool want_ll, const float *d_sw, floa
         select_row_pass<Sh>(r.packed, from_p, want_ll, thresh < plsa::TINY_THRESH, [&](auto SS, auto FP, auto LL, auto TN) {
             Scope s(c, from_p ? "k_row_pass<P>" : want_ll ? "k_row_pass<fused,LL>" : "k_row_pass<fused>");
             hipLaunchKernelGGL((plsa::k_row_pass<decltype(SS), decltype(FP)::value, decltype(LL)::value, decltype(TN)::value>),
-                               dim3(r.plan.grid), dim3(256), 0, c->ls, r.indptr, r.colidx, r.vals, n, r.order, U, Vt, p_base(c), Un,
+                               dim3(r.plan.grid), dim3(256), 0, c->ls, r.indptr, r.colidx, r.vals, r.sblk, n, r.order, U, Vt, p_base(c),
+                               Un,
                                d_sw, d_norm_pdz, kp, thresh, r.ll_partials, r.ritem_row, r.ritem_start, r.rseg, r.n_ritems,
                                r.rpartial, r.xcd_rows ? 1 : 0);
         });
@@ -889,6 +898,7 @@ struct ColLaunch {
     i64 n_items;
     const int *csc_row, *csc_pos;    // csc_row: the packed CSC stream when `packed`
     const float *csc_val;
+    int slot;                        // `packed`: words per item slot of the stream
     float *partial;                  // one k-vector per item
     double *colsum_rows, *colsum_rows2;   // one float64 sum row per chunk; stage-2 rows of the norm (plan.norm_blocks of them)
     float *norm_pwz;
@@ -908,6 +918,7 @@ int prepare_col_pass(plsa_ctx *c, bool from_p, ColLaunch &l) {
     l.item_rec = c->csc.item_rec.as<int4>(); l.n_items = c->csc.n_items;
     l.csc_row = l.packed ? c->pk_csc.buf.as<int>() : c->csc.row.as<int>();
     l.csc_pos = c->csc.pos.as<int>(); l.csc_val = c->csc.val.as<float>();
+    l.slot = l.packed ? plsa::plan::line_slot(c->pk_csc.seg, c->pk_csc.lpn) : 0;
     l.partial = c->partial.as<float>(); l.norm_pwz = c->norm_pwz.as<float>();
     l.colsum_rows = c->colsum_rows.as<double>(); l.colsum_rows2 = c->colsum_rows2.as<double>();
     l.item_first = c->csc.item_first.as<int>(); l.heavy_cols = c->csc.heavy_cols.as<int>();
@@ -941,7 +952,8 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
                 unsigned long long *te = c->t_end.as<unsigned long long>();
                 select_col_pass<Sh>(l.packed, from_p, timed, thresh < plsa::TINY_THRESH, [&](auto SS, auto FP, auto TM, auto TN) {
                     hipLaunchKernelGGL((plsa::k_col_pass<decltype(SS), decltype(FP)::value, decltype(TM)::value, decltype(TN)::value>),
-                                       dim3(grid), dim3(256), smem, c->ls, l.item_rec, l.n_items, lo, l.csc_row, l.csc_val, l.csc_pos,
+                                       dim3(grid), dim3(256), smem, c->ls, l.item_rec, l.n_items, lo, l.csc_row, l.csc_val, l.slot,
+                                       l.csc_pos,
                                        U, Vt, p_base(c), d_sw, l.partial, kp, thresh, l.xcd_split, l.colsum_rows, te);
                 });
                 return launch_check(c, "k_col_pass");

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plsa_launch_plan.hpp"
+
 #ifndef PLSA_UNR
 #define PLSA_UNR 4      // non-zeros whose gathers are in flight together, per group
 #endif
@@ -121,8 +123,9 @@ struct Shape {
 };
 
 // Packed entry stream of the fused passes (k_row_pass / k_col_pass with FROM_P = false): one 32-bit word per non-zero,
-// e = id | code << 24, position-parallel to the (id, count) arrays it was packed from.  code = the count when that is an
-// integer in 1..255, else 0: an ESCAPE, the count is then read from the float array at the same position.  (float)code is
+// e = id | code << 24, laid out in blocks of 4 * LPN words per document or item (the line layout, plsa_launch_plan.hpp;
+// EntryCursor below reads it).  code = the count when that is an integer in 1..255, else 0: an ESCAPE, the count is then
+// read from the float array, which keeps the entry's original position.  (float)code is
 // exactly the count, so both forms feed the same x to the same arithmetic; the index stream shrinks from 8 to 4 bytes per
 // entry.  The flag rides on the shape type (Packed<S>) rather than behind it: the kernels' own template flags, which
 // the profiling tools read from the kernel names, stay as they are.
@@ -142,6 +145,63 @@ __device__ __forceinline__ void unpack_entry(int &id, float &x, const float *__r
     x = (float)(e >> 24);                          // v_cvt_f32_ubyte3
     if (x == 0.f && j < j_end) x = ldf(vals + j);
 }
+
+// words per row-item slot of a document stream in the line layout (plan::line_slot, a power-of-two block: shifts)
+template <int LPN>
+__device__ __forceinline__ int row_item_slot(int rseg) { return (rseg + 4 * LPN - 1) / (4 * LPN) * (4 * LPN); }
+
+// The entry stream of one owner (a document, a row item, a column item) as the fused passes and the NMF walk it: LPN entries
+// per batch, lane li takes entry jb + li of the batch at jb, and what the following batches need is in flight while the
+// current one is consumed.
+//   two arrays : one id and one count per lane and batch, the next batch's pair requested when the current is handed out.
+//   S::PACKED  : the line layout (plsa_launch_plan.hpp).  `sbase` is the owner's first word (a multiple of the block); the
+//     lane holds ONE block as a 16-byte vector and batch c takes component c, so four batches cost one load per lane.  The
+//     next block is requested when the LAST component has been taken: only then are the vector's registers free (three more
+//     than a word, not seven), and the request still has that whole batch of gathers to hide under -- the distance the
+//     one-word loads had.  `c` is wave-uniform: the groups of a wave open their owners together and step together.
+// take() hands out the batch at jb: (id, count) of entry jb + li, (0, 0) past j1 -- a pad word is 0 and not an escape
+// (unpack_entry's j < j_end).  An escaped entry reads its count from vals[jb + li]: the arrays keep their positions.
+template <class S>
+struct EntryCursor {
+    static constexpr int LPN = S::LPN;
+    int4 cur;      // PACKED: the lane's words of the current block; two arrays: cur.x = the next batch's id
+    float x_n;     // two arrays: the next batch's count
+    int soff, c;   // PACKED: soff + j = the lane's vector in the block that starts with entry j; c = component of the next batch
+
+    __device__ __forceinline__ static int4 ld_block(const int *p) {
+        typedef int i4v __attribute__((ext_vector_type(4)));
+        const i4v *q = reinterpret_cast<const i4v *>(p);
+        const i4v t = PLSA_NT_STREAMS ? __builtin_nontemporal_load(q) : *q;   // global_load_dwordx4
+        return make_int4(t.x, t.y, t.z, t.w);
+    }
+    __device__ __forceinline__ void open(const int *__restrict__ ids, const float *__restrict__ vals, int sbase, int j0, int j1,
+                                         int li) {
+        if constexpr (S::PACKED) {
+            soff = sbase - j0 + 4 * li;
+            c = 0;
+            cur = j0 < j1 ? ld_block(ids + soff + j0) : make_int4(0, 0, 0, 0);
+        } else {
+            cur.x = (j0 + li < j1) ? ldi(ids + j0 + li) : 0;
+            x_n = (j0 + li < j1) ? ldf(vals + j0 + li) : 0.f;
+        }
+    }
+    __device__ __forceinline__ void take(const int *__restrict__ ids, const float *__restrict__ vals, int jb, int j1, int li,
+                                         int &id_l, float &x_l) {
+        if constexpr (S::PACKED) {
+            id_l = c == 0 ? cur.x : c == 1 ? cur.y : c == 2 ? cur.z : cur.w;
+            // unpacked BEFORE the next block is requested: an escape load then waits for itself only
+            unpack_entry(id_l, x_l, vals, jb + li, j1);
+            if (c == 3) cur = (jb + LPN < j1) ? ld_block(ids + soff + jb + LPN) : make_int4(0, 0, 0, 0);
+            c = (c + 1) & 3;
+        } else {
+            id_l = cur.x;
+            x_l = x_n;
+            const int jn = jb + LPN + li;
+            cur.x = jn < j1 ? ldi(ids + jn) : 0;
+            x_n = jn < j1 ? ldf(vals + jn) : 0.f;
+        }
+    }
+};
 
 // gather the lane's chunks of one factor row WITHOUT a branch: out-of-row chunks read offset 0
 // (a valid address) -- ZERO_INVALID then forces them to zero (needed for one operand only:
@@ -369,7 +429,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_e_step_rows(const int *__re
 template <class S, bool FROM_P, bool WANT_LL, bool TINY>
 __device__ __forceinline__ void row_pass_body(const int *__restrict__ indptr,
                                                   const int *__restrict__ colidx,
-                                                  const float *__restrict__ vals, int n,
+                                                  const float *__restrict__ vals, const int *__restrict__ sblk, int n,
                                                   const int *__restrict__ row_order,
                                                   const float *__restrict__ U,
                                                   const float *__restrict__ Vt,
@@ -406,18 +466,14 @@ __device__ __forceinline__ void row_pass_body(const int *__restrict__ indptr,
 #pragma unroll
         for (int j = 0; j < CH; ++j) acc[j] = zero4();
         const float swd = (WANT_LL && sw) ? sw[d] : 1.0f;
-        // software-pipelined index stream: the next LPN (word, count) pairs are in flight while the
-        // current ones are consumed (S::PACKED: one packed word per entry, colidx holds the packed stream)
-        int w_n = (j0 + li < j1) ? ldi(colidx + j0 + li) : 0;
-        float x_n = (!S::PACKED && j0 + li < j1) ? ldf(vals + j0 + li) : 0.f;
+        // software-pipelined entry stream (EntryCursor; S::PACKED: colidx holds the packed stream in the line layout, a document
+        // starts at block sblk[d], row item r owns slot r)
+        EntryCursor<S> es;
+        es.open(colidx, vals, S::PACKED ? (items ? (int)r * row_item_slot<LPN>(rseg) : sblk[d] * (4 * LPN)) : 0, j0, j1, li);
         for (int jb = j0; jb < j1; jb += LPN) {
-            int w_l = w_n;
-            float x_l = x_n;
-            // unpacked BEFORE the next words are requested: an escape load then waits for itself only
-            if (S::PACKED) unpack_entry(w_l, x_l, vals, jb + li, j1);
-            const int jn = jb + LPN + li;
-            w_n = jn < j1 ? ldi(colidx + jn) : 0;
-            if (!S::PACKED) x_n = jn < j1 ? ldf(vals + jn) : 0.f;
+            int w_l;
+            float x_l;
+            es.take(colidx, vals, jb, j1, li, w_l, x_l);
             const int cnt = min(LPN, j1 - jb);
             for (int s0 = 0; s0 < cnt; s0 += UNR) {
                 float4 a[UNR][CH];   // Vt rows (fused) or P rows (FROM_P)
@@ -525,7 +581,7 @@ __device__ __forceinline__ void row_pass_body(const int *__restrict__ indptr,
 template <class S, bool FROM_P, bool WANT_LL, bool TINY = false>
 __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restrict__ indptr,
                                                   const int *__restrict__ colidx,
-                                                  const float *__restrict__ vals, int n,
+                                                  const float *__restrict__ vals, const int *__restrict__ sblk, int n,
                                                   const int *__restrict__ row_order,
                                                   const float *__restrict__ U,
                                                   const float *__restrict__ Vt,
@@ -537,7 +593,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass(const int *__restr
                                                   const int *__restrict__ ritem_row,
                                                   const int *__restrict__ ritem_start, int rseg,
                                                   i64 n_ritems, float *__restrict__ rpartial, int xcd_rows) {
-    row_pass_body<S, FROM_P, WANT_LL, TINY>(indptr, colidx, vals, n, row_order, U, Vt, P, U_new, sw, norm_pdz_out, kp_rt, thresh,
+    row_pass_body<S, FROM_P, WANT_LL, TINY>(indptr, colidx, vals, sblk, n, row_order, U, Vt, P, U_new, sw, norm_pdz_out, kp_rt, thresh,
                                             ll_partials, ritem_row, ritem_start, rseg, n_ritems, rpartial, xcd_rows,
                                             blockIdx.x, gridDim.x);
 }
@@ -710,7 +766,7 @@ template <class S, bool FROM_P, bool TIMED, bool TINY>
 __device__ __forceinline__ void col_pass_body(const int4 *__restrict__ item_rec, i64 n_items,
                                                   const int *__restrict__ xcd_lo,
                                                   const int *__restrict__ csc_row,
-                                                  const float *__restrict__ csc_val,
+                                                  const float *__restrict__ csc_val, int slot,
                                                   const int *__restrict__ csc_pos,
                                                   const float *__restrict__ U,
                                                   const float *__restrict__ Vt,
@@ -740,17 +796,15 @@ __device__ __forceinline__ void col_pass_body(const int4 *__restrict__ item_rec,
             const int w = rec.x, j0 = rec.y, j1 = rec.z;
             float4 vt[CH];
             load_row<S, true, PLSA_NT_STREAMS>(Vt + (i64)w * kp, li, kp, vt);
-            int d_n = (j0 + li < j1) ? ldi(csc_row + j0 + li) : 0;
-            float x_n = (!S::PACKED && j0 + li < j1) ? ldf(csc_val + j0 + li) : 0.f;
+            EntryCursor<S> es;                 // (see k_row_pass; S::PACKED: item rec.w owns slot rec.w of `slot` words)
+            es.open(csc_row, csc_val, S::PACKED ? rec.w * slot : 0, j0, j1, li);
             int p_n = (FROM_P && j0 + li < j1) ? ldi(csc_pos + j0 + li) : 0;
             for (int jb = j0; jb < j1; jb += LPN) {
-                int d_l = d_n;
+                int d_l;
                 const int p_l = p_n;
-                float x_l = x_n;
-                if (S::PACKED) unpack_entry(d_l, x_l, csc_val, jb + li, j1);   // (see k_row_pass)
+                float x_l;
+                es.take(csc_row, csc_val, jb, j1, li, d_l, x_l);
                 const int jn = jb + LPN + li;
-                d_n = jn < j1 ? ldi(csc_row + jn) : 0;
-                if (!S::PACKED) x_n = jn < j1 ? ldf(csc_val + jn) : 0.f;
                 if (FROM_P) p_n = jn < j1 ? ldi(csc_pos + jn) : 0;
                 if (sw) x_l *= sw[d_l];  // t = s * sample_weight[d]  (plsa.py:294), folded into the count
                 const int cnt = min(LPN, j1 - jb);
@@ -777,7 +831,7 @@ template <class S, bool FROM_P, bool TIMED, bool TINY = false>
 __global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__restrict__ item_rec, i64 n_items,
                                                   const int *__restrict__ xcd_lo,
                                                   const int *__restrict__ csc_row,
-                                                  const float *__restrict__ csc_val,
+                                                  const float *__restrict__ csc_val, int slot,
                                                   const int *__restrict__ csc_pos,
                                                   const float *__restrict__ U,
                                                   const float *__restrict__ Vt,
@@ -787,7 +841,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass(const int4 *__
                                                   int xcd_split, double *__restrict__ chunk_sums,
                                                   unsigned long long *__restrict__ t_end) {
     extern __shared__ double scol[];   // [GPB][kp]: sum of the chunk's accumulators (-> norm_pwz)
-    col_pass_body<S, FROM_P, TIMED, TINY>(item_rec, n_items, xcd_lo, csc_row, csc_val, csc_pos, U, Vt, P, sw, partial, kp_rt, thresh,
+    col_pass_body<S, FROM_P, TIMED, TINY>(item_rec, n_items, xcd_lo, csc_row, csc_val, slot, csc_pos, U, Vt, P, sw, partial, kp_rt, thresh,
                                           xcd_split, chunk_sums, t_end, scol, blockIdx.x, gridDim.x);
 }
 
@@ -1245,36 +1299,61 @@ __device__ __forceinline__ void add_escapes(unsigned esc, unsigned long long *__
     for (int o = 32; o > 0; o >>= 1) esc += __shfl_xor(esc, o, 64);
     if ((threadIdx.x & 63) == 0 && esc) atomicAdd(n_esc, (unsigned long long)esc);
 }
-// packed entry words of a stream (see Packed): packed[i] = ids[i] | pack_code(vals[i]) << 24, escapes counted into *n_esc
-__global__ __launch_bounds__(256) void k_pack_entries(const int *__restrict__ ids, const float *__restrict__ vals, i64 nnz,
-                                                      unsigned *__restrict__ packed, unsigned long long *__restrict__ n_esc) {
+// Packed entry stream of a pass (see Packed) in the line layout (plsa_launch_plan.hpp): one thread per stream WORD -- block,
+// lane and component from the word's position, the owner from the block, the entry from those -- so that pad words are
+// written (0) by the same pass and no write is scattered.  Owners:
+//   documents (blk != nullptr): `blk` holds the n_owners + 1 block offsets, the owner of a block by bisection; entries
+//     [ptr[d], ptr[d + 1])
+//   items (blk == nullptr): slot it = word / slot; entries [item_start[it], end), end = item_end[it] (column items), or
+//     min(start + seg, ptr[item_row[it] + 1]) (row items: item_end == nullptr)
+// Escapes (valid entries whose count does not fit the code) are counted into *n_esc.
+__global__ __launch_bounds__(256) void k_pack_entries(const int *__restrict__ ids, const float *__restrict__ vals, i64 n_words,
+                                                      int lpn, const int *__restrict__ blk, const int *__restrict__ ptr,
+                                                      int n_owners, const int *__restrict__ item_start,
+                                                      const int *__restrict__ item_end, const int *__restrict__ item_row,
+                                                      int seg, int slot, unsigned *__restrict__ packed,
+                                                      unsigned long long *__restrict__ n_esc) {
     unsigned esc = 0;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (i64)gridDim.x * blockDim.x) {
-        const unsigned code = pack_code(vals[i]);
-        packed[i] = (unsigned)ids[i] | (code << 24);
-        esc += code == 0u;
+    const int block_words = plan::line_block(lpn);
+    for (i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x; p < n_words; p += (i64)gridDim.x * blockDim.x) {
+        int j0, j_end;
+        i64 word;          // offset from the owner's first word
+        if (blk) {
+            const int b = (int)(p / block_words);
+            int lo = 0, hi = n_owners - 1;         // the last d with blk[d] <= b (empty documents share their successor's offset)
+            while (lo < hi) {
+                const int mid = (int)(((i64)lo + hi + 1) >> 1);
+                if (blk[mid] <= b) lo = mid; else hi = mid - 1;
+            }
+            j0 = ptr[lo]; j_end = ptr[lo + 1];
+            word = p - (i64)blk[lo] * block_words;
+        } else {
+            const i64 it = p / slot;
+            j0 = item_start[it];
+            j_end = item_end ? item_end[it] : min(j0 + seg, ptr[item_row[it] + 1]);
+            word = p - it * slot;
+        }
+        const i64 rel = plan::line_rel(plan::line_pos_of_word(word, lpn), lpn);
+        unsigned e = 0u;
+        if (rel < (i64)(j_end - j0)) {
+            const i64 j = j0 + rel;
+            const unsigned code = pack_code(vals[j]);
+            e = (unsigned)ids[j] | (code << 24);
+            esc += code == 0u;
+        }
+        packed[p] = e;
     }
     add_escapes(esc, n_esc);
 }
-// CSC arrays in column order; `packed` (optional): the column pass' packed entry stream, escapes counted into *n_esc
+// CSC arrays in column order (the column pass' packed stream is k_pack_entries' over the column items, once they are cut)
 __global__ __launch_bounds__(256) void k_csc_gather(const int *__restrict__ pos, const int *__restrict__ rowidx,
                                                     const float *__restrict__ vals, i64 nnz, int *__restrict__ csc_row,
-                                                    float *__restrict__ csc_val, unsigned *__restrict__ packed,
-                                                    unsigned long long *__restrict__ n_esc) {
-    unsigned esc = 0;
+                                                    float *__restrict__ csc_val) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (i64)gridDim.x * blockDim.x) {
         const int p = pos[i];
-        const int r = rowidx[p];
-        const float v = vals[p];
-        csc_row[i] = r;
-        csc_val[i] = v;
-        if (packed) {
-            const unsigned code = pack_code(v);
-            packed[i] = (unsigned)r | (code << 24);
-            esc += code == 0u;
-        }
+        csc_row[i] = rowidx[p];
+        csc_val[i] = vals[p];
     }
-    if (packed) add_escapes(esc, n_esc);
 }
 // items per row of a CSR / column of a CSC: a row is cut into pieces of <= seg entries (documents: k_ritem_fill; columns: k_item_fill)
 __global__ void k_item_counts(const int *__restrict__ colptr, int m, int seg, int *__restrict__ cnt) {

@@ -3,7 +3,8 @@
 // structure builders compute on the host: sort bits, the E-step's piece length, the packing rule.  Plain values in, plain
 // values out: no context, no device memory, no environment.  plsa_hip.hip's prepare_row_pass / prepare_col_pass turn these
 // into the structures (built by plsa_structures.hpp), scratch and grids of one pass (the fit, the batched members and the
-// NMF all launch from those); tests/launch_plan_host.cpp runs every function on a CPU.
+// NMF all launch from those); tests/launch_plan_host.cpp runs every function on a CPU (the line layout of the packed
+// streams: tests/line_stream_plan_host.cpp).
 #pragma once
 
 #include <algorithm>
@@ -120,6 +121,35 @@ constexpr int64_t PACK_ID_RANGE = (int64_t)1 << 24;
 inline bool packed_ok(int64_t nnz, int64_t id_range, uint64_t escaped) {
     return nnz > 0 && id_range <= PACK_ID_RANGE && escaped * 16 <= (uint64_t)nnz;
 }
+
+// Line layout of a packed entry stream.  The stream's OWNERS (documents, row items, column items) each start on a BLOCK of
+// 4 * lpn words, lpn = the lane count of the pass that reads the stream; pad words are 0.  Lane li of a group loads ONE
+// 16-byte vector per block, the words 4 * li .. 4 * li + 3, and batch c (0..3) of the block consumes component c: the word
+// at 4 * li + c holds entry c * lpn + li of the block -- the entry that lane handles in that batch with one word per load.
+// From 8 lanes on a group's load is one or two whole 128-byte lines.
+//   documents: padded to whole blocks, one array of n + 1 block offsets (the start of document d in BLOCKS)
+//   items (row items, column items): one slot of line_slot(seg, lpn) words per item, at slot index = item id
+// Word offsets inside the kernels are 32-bit: a stream of more than LINE_MAX_WORDS words is not built (its pass runs on the
+// two arrays).
+constexpr int64_t LINE_MAX_WORDS = ((int64_t)1 << 31) - 1;
+constexpr int line_block(int lpn) { return 4 * lpn; }
+constexpr int64_t line_blocks(int64_t len, int lpn) { return (len + line_block(lpn) - 1) / line_block(lpn); }
+constexpr int line_slot(int seg, int lpn) { return (int)(line_blocks(seg, lpn) * line_block(lpn)); }
+// entry `rel` of an owner (0 = its first) <-> (block of the owner, lane, component) <-> word offset from the owner's start
+struct LinePos { int64_t block; int lane, comp; };
+constexpr LinePos line_pos(int64_t rel, int lpn) {
+    return LinePos{rel / line_block(lpn), (int)(rel % line_block(lpn) % lpn), (int)(rel % line_block(lpn) / lpn)};
+}
+constexpr int64_t line_rel(const LinePos &p, int lpn) { return p.block * line_block(lpn) + (int64_t)p.comp * lpn + p.lane; }
+constexpr int64_t line_word(const LinePos &p, int lpn) { return p.block * line_block(lpn) + 4 * (int64_t)p.lane + p.comp; }
+constexpr LinePos line_pos_of_word(int64_t word, int lpn) {
+    return LinePos{word / line_block(lpn), (int)(word % line_block(lpn) / 4), (int)(word % 4)};
+}
+// the most words a document stream can take (every document wastes less than a block), known before the offsets are summed;
+// the words of an item stream; whether a stream of that many words is built
+constexpr int64_t line_doc_words_bound(int64_t nnz, int64_t n, int lpn) { return nnz + n * (line_block(lpn) - 1); }
+constexpr int64_t line_item_words(int64_t n_items, int seg, int lpn) { return n_items * line_slot(seg, lpn); }
+constexpr bool line_stream_fits(int64_t words) { return words <= LINE_MAX_WORDS; }
 
 inline int grid_for(int64_t work, int per_block, int cap) {
     int64_t need = (work + per_block - 1) / per_block;

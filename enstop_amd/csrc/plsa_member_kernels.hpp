@@ -25,6 +25,7 @@ struct MemberArgs {
     const int4 *item_rec;
     const int *csc_row;            // the packed CSC stream in a packed group
     const float *csc_val;
+    int slot;                      // words per item slot of the packed CSC stream
     float *partial;
     double *chunk_sums;
     i64 n_items;
@@ -37,6 +38,7 @@ struct MemberArgs {
     // document pass
     const int *indptr, *colidx;    // colidx: the packed CSR stream in a packed group
     const float *vals;
+    const int *sblk;               // block offsets of the documents in the packed CSR stream
     const int *row_order, *ritem_row, *ritem_start, *ritem_first;   // ritem_*: nullptr for a member on whole rows
     float *rpartial;
     double *ll_partials, *ll_out;
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES) void k_row_pass_members(const Memb
     const MemberArgs &a = args[r];
     if (blockIdx.x >= (unsigned)a.row_grid) return;
     const int pu = (int)((cu >> r) & 1ull), pv = (int)((cv >> r) & 1ull);
-    row_pass_body<S, false, WANT_LL, TINY>(a.indptr, a.colidx, a.vals, a.n, a.row_order, a.U[pu], a.Vt[pv], nullptr, a.U[1 - pu],
+    row_pass_body<S, false, WANT_LL, TINY>(a.indptr, a.colidx, a.vals, a.sblk, a.n, a.row_order, a.U[pu], a.Vt[pv], nullptr, a.U[1 - pu],
                                            nullptr, nullptr, kp_rt, thresh, a.ll_partials, a.ritem_row, a.ritem_start, a.rseg,
                                            a.n_ritems, a.rpartial, 0, blockIdx.x, (unsigned)a.row_grid);
 }
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(256, PLSA_WAVES_COL) void k_col_pass_members(const 
     if (blockIdx.x >= (unsigned)a.n_chunks) return;
     const int pu = (int)((cu >> r) & 1ull), pv = (int)((cv >> r) & 1ull);
     const unsigned nblocks = min((unsigned)a.n_chunks, gridDim.x);
-    col_pass_body<S, false, false, TINY>(a.item_rec, a.n_items, nullptr, a.csc_row, a.csc_val, nullptr, a.U[pu], a.Vt[pv], nullptr,
+    col_pass_body<S, false, false, TINY>(a.item_rec, a.n_items, nullptr, a.csc_row, a.csc_val, a.slot, nullptr, a.U[pu], a.Vt[pv], nullptr,
                                          nullptr, a.partial, kp_rt, thresh, 0, a.chunk_sums, nullptr, scol, blockIdx.x, nblocks);
 }
 

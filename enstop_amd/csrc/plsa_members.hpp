@@ -88,6 +88,7 @@ int member_args(plsa_ctx *c, double *ll_out, plsa::MemberArgs &a, plsa_members::
     a.item_rec = l.item_rec;
     a.csc_row = l.csc_row;
     a.csc_val = l.csc_val;
+    a.slot = l.slot;
     a.partial = l.partial;
     a.chunk_sums = l.colsum_rows;
     a.n_items = l.n_items;
@@ -104,6 +105,7 @@ int member_args(plsa_ctx *c, double *ll_out, plsa::MemberArgs &a, plsa_members::
     a.indptr = r.indptr;
     a.colidx = r.colidx;
     a.vals = r.vals;
+    a.sblk = r.sblk;
     a.row_order = r.order;
     a.ritem_row = r.ritem_row;
     a.ritem_start = r.ritem_start;

@@ -54,7 +54,7 @@ int nmf_run_update_w(plsa_ctx *c, int iters) {
         auto launch = [&](auto SS) {
             Scope s(c, "k_nmf_row_pass");
             hipLaunchKernelGGL((plsa::k_nmf_row_pass<decltype(SS)>), dim3(r.plan.grid), dim3(256), 0, c->ls, r.indptr, r.colidx,
-                               r.vals, n, r.order, W, Vt, hs, kp, iters, r.ritem_row, r.ritem_start, r.rseg, r.n_ritems, r.rpartial);
+                               r.vals, r.sblk, n, r.order, W, Vt, hs, kp, iters, r.ritem_row, r.ritem_start, r.rseg, r.n_ritems, r.rpartial);
         };
         if (r.packed) launch(plsa::Packed<Sh>{}); else launch(Sh{});
         if (r.items) {
@@ -79,7 +79,7 @@ int nmf_run_update_h(plsa_ctx *c) {
         auto launch = [&](auto SS) {
             Scope s(c, "k_nmf_col_pass");
             hipLaunchKernelGGL((plsa::k_nmf_col_pass<decltype(SS)>), dim3(grid), dim3(256), 0, c->ls, l.item_rec, l.n_items,
-                               l.csc_row, l.csc_val, W, Vt, l.partial, c->kp);
+                               l.csc_row, l.csc_val, l.slot, W, Vt, l.partial, c->kp);
         };
         if (l.packed) launch(plsa::Packed<Sh>{}); else launch(Sh{});
     }));

@@ -76,21 +76,19 @@ __device__ __forceinline__ void nmf_batch(int s0, int id_l, float x_l, int li, i
     for (int q = 0; q < UN; ++q) nmf_axpy<CH>(acc, __shfl(q_mine, s0 + q, LPN), a[q]);
 }
 
-// one sweep over the entries [j0, j1) of a stream (CSR piece of a document, CSC piece of a column item)
+// one sweep over the entries [j0, j1) of a stream (CSR piece of a document, CSC piece of a column item); sbase: the owner's
+// first word in a packed stream (plsa_kernels.hpp: EntryCursor)
 template <class S, int UN>
-__device__ __forceinline__ void nmf_sweep(const int *__restrict__ ids, const float *__restrict__ vals, int j0, int j1,
+__device__ __forceinline__ void nmf_sweep(const int *__restrict__ ids, const float *__restrict__ vals, int sbase, int j0, int j1,
                                           int li, int kp, const float *table, const float4 (&own)[S::CH],
                                           float4 (&acc)[S::CH]) {
     constexpr int LPN = S::LPN;
-    int id_n = (j0 + li < j1) ? ldi(ids + j0 + li) : 0;
-    float x_n = (!S::PACKED && j0 + li < j1) ? ldf(vals + j0 + li) : 0.f;
+    EntryCursor<S> es;
+    es.open(ids, vals, sbase, j0, j1, li);
     for (int jb = j0; jb < j1; jb += LPN) {
-        int id_l = id_n;
-        float x_l = x_n;
-        if (S::PACKED) unpack_entry(id_l, x_l, vals, jb + li, j1);
-        const int jn = jb + LPN + li;
-        id_n = jn < j1 ? ldi(ids + jn) : 0;
-        if (!S::PACKED) x_n = jn < j1 ? ldf(vals + jn) : 0.f;
+        int id_l;
+        float x_l;
+        es.take(ids, vals, jb, j1, li, id_l, x_l);
         const int cnt = min(LPN, j1 - jb);
         int s0 = 0;
         for (; s0 + UN <= cnt; s0 += UN) nmf_batch<S, UN>(s0, id_l, x_l, li, kp, table, own, acc);
@@ -111,7 +109,7 @@ __device__ __forceinline__ void nmf_sweep(const int *__restrict__ ids, const flo
 // ------------------------------------------------------------------------------------------------
 template <class S>
 __global__ __launch_bounds__(256) void k_nmf_row_pass(const int *__restrict__ indptr, const int *__restrict__ colidx,
-                                                      const float *__restrict__ vals, int n,
+                                                      const float *__restrict__ vals, const int *__restrict__ sblk, int n,
                                                       const int *__restrict__ row_order, float *W,
                                                       const float *__restrict__ Vt, const float *__restrict__ h_sum,
                                                       int kp_rt, int iters, const int *__restrict__ ritem_row,
@@ -132,10 +130,11 @@ __global__ __launch_bounds__(256) void k_nmf_row_pass(const int *__restrict__ in
         const int j1 = items ? min(j0 + rseg, indptr[d + 1]) : indptr[d + 1];
         float4 w[CH], acc[CH];
         load_row<S, true>(W + (i64)d * kp, li, kp, w);
+        const int sbase = S::PACKED ? (items ? (int)r * row_item_slot<LPN>(rseg) : sblk[d] * (4 * LPN)) : 0;
         for (int it = 0; it < iters; ++it) {
 #pragma unroll
             for (int j = 0; j < CH; ++j) acc[j] = zero4();
-            nmf_sweep<S, S::UNR>(colidx, vals, j0, j1, li, kp, Vt, w, acc);
+            nmf_sweep<S, S::UNR>(colidx, vals, sbase, j0, j1, li, kp, Vt, w, acc);
             if (items) break;
 #pragma unroll
             for (int j = 0; j < CH; ++j) w[j] = S::ok(li, j, kp) ? nmf_scale(w[j], acc[j], hs[j]) : zero4();
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(256) void k_nmf_row_reduce(const int *__restrict__ 
 template <class S>
 __global__ __launch_bounds__(256) void k_nmf_col_pass(const int4 *__restrict__ item_rec, i64 n_items,
                                                       const int *__restrict__ csc_row, const float *__restrict__ csc_val,
-                                                      const float *__restrict__ W, const float *__restrict__ Vt,
+                                                      int slot, const float *__restrict__ W, const float *__restrict__ Vt,
                                                       float *__restrict__ partial, int kp_rt) {
     constexpr int LPN = S::LPN, CH = S::CH;
     constexpr int GPB = 256 / LPN;
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(256) void k_nmf_col_pass(const int4 *__restrict__ i
         load_row<S, true>(Vt + (i64)rec.x * kp, li, kp, h);
 #pragma unroll
         for (int j = 0; j < CH; ++j) acc[j] = zero4();
-        nmf_sweep<S, S::UNR_COL>(csc_row, csc_val, rec.y, rec.z, li, kp, W, h, acc);
+        nmf_sweep<S, S::UNR_COL>(csc_row, csc_val, S::PACKED ? rec.w * slot : 0, rec.y, rec.z, li, kp, W, h, acc);
 #pragma unroll
         for (int j = 0; j < CH; ++j)
             if (S::ok(li, j, kp)) st4(partial + (i64)rec.w * kp + S::c4(li, j), acc[j]);

@@ -33,13 +33,20 @@ void set_shape(plsa_ctx *c, int k) {
     c->row_lpn = sh.row_lpn; c->row_ch = sh.row_ch;
     // the row-item decision and length follow the DOCUMENT pass' lane count (ensure_ritems), which changes between
     // kp = 60 and kp = 64 while lpn stays 16: watched on its own
+    // a packed stream is laid out in blocks of four words per lane of ITS pass (plsa_launch_plan.hpp: line layout): the
+    // document stream follows the document pass' lane count (and the row items), the column stream the column pass'
     if (c->row_lpn != prev_row_lpn) {
         c->ritems.invalidate();
+        c->pk_csr.invalidate();
         c->struct_row_lpn = c->row_lpn;
     }
     if (lpn != prev_lpn) {        // column item lengths depend on the lane shape
         c->eitems.invalidate();
-        if (!c->seg_override) { c->csc.invalidate(); c->pk_csc.invalidate(); }   // (the CSC gather writes its packed stream)
+        if (!c->seg_override) c->csc.invalidate();
+        // the column stream goes with the CSC copy, or -- the copy stays (PLSA_COL_SEG) -- is written again for the new lane
+        // count by the next ensure_csc, as it was written with the copy
+        c->pk_csc.reshape = c->seg_override && (c->pk_csc.valid || c->pk_csc.reshape);
+        c->pk_csc.invalidate();
         c->struct_lpn = lpn;
     }
 }
@@ -174,19 +181,19 @@ int ensure_eitems(plsa_ctx *c, int eseg) {
 // that writes the stream: packed_begin before it, packed_finish after it.  An ineligible stream is not kept: its pass runs
 // on the two arrays.
 // ---------------------------------------------------------------------------------------------
-// *pack: the stream is worth writing (`id_range` ids); then its buffer and the zeroed escape counter are ready
-int packed_begin(plsa_ctx *c, plsa_ctx::PackedStream &s, i64 id_range, bool *pack) {
+// *pack: the stream is worth writing (`id_range` ids, at most `words_bound` words); then the zeroed escape counter is ready
+int packed_begin(plsa_ctx *c, plsa_ctx::PackedStream &s, i64 id_range, i64 words_bound, bool *pack) {
     s.invalidate();
     s.ok = false;
-    *pack = c->packed && plsa::plan::packed_ok(c->nnz, id_range, 0);
+    s.reshape = false;
+    *pack = c->packed && plsa::plan::packed_ok(c->nnz, id_range, 0) && plsa::plan::line_stream_fits(words_bound);
     if (!*pack) return 0;
-    CHK(ensure(c, s.buf, sizeof(unsigned) * (size_t)c->nnz));
     CHK(ensure(c, c->pk_count, sizeof(unsigned long long)));
     HIPCHK(c, hipMemsetAsync(c->pk_count.p, 0, sizeof(unsigned long long), c->stream));
     return 0;
 }
 
-// the escape count read back (a written stream: the host waits for c->stream), the decision, the buffer of a loser freed
+// the escape count read back (a written stream: the host waits for c->stream), the decision, the buffers of a loser freed
 int packed_finish(plsa_ctx *c, plsa_ctx::PackedStream &s, i64 id_range, bool pack) {
     unsigned long long escaped = 0;
     if (pack) {
@@ -194,21 +201,64 @@ int packed_finish(plsa_ctx *c, plsa_ctx::PackedStream &s, i64 id_range, bool pac
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     s.ok = pack && plsa::plan::packed_ok(c->nnz, id_range, escaped);
-    if (!s.ok) s.buf.release();
+    if (!s.ok) { s.buf.release(); s.blk.release(); }
     s.valid = true;
     return 0;
 }
 
-// a stream from its (id, count) arrays
-int build_packed(plsa_ctx *c, plsa_ctx::PackedStream &s, const int *ids, const float *vals, i64 id_range) {
-    bool pack = false;
-    CHK(packed_begin(c, s, id_range, &pack));
-    if (pack) {
-        hipLaunchKernelGGL(plsa::k_pack_entries, dim3(grid_for(c, c->nnz, 256)), dim3(256), 0, c->stream,
-                           ids, vals, c->nnz, s.buf.as<unsigned>(), c->pk_count.as<unsigned long long>());
-        CHK(launch_check(c, "k_pack_entries"));
+// the words of a stream in the line layout for `lpn` lanes.  Whole documents (seg == 0): s.blk gets their block offsets (the
+// count of blocks per document and its exclusive sum, like the items of a cut); items of `seg` entries: one slot each,
+// entries [item_start[i], item_end[i]) or -- item_end == nullptr, row items -- up to the end of document item_row[i]
+int write_packed(plsa_ctx *c, plsa_ctx::PackedStream &s, const int *ids, const float *vals, int lpn, int seg, i64 n_items,
+                 const int *item_start, const int *item_end, const int *item_row) {
+    s.lpn = lpn; s.seg = seg;
+    const int block = plsa::plan::line_block(lpn), slot = seg > 0 ? plsa::plan::line_slot(seg, lpn) : 0;
+    auto pack = [&](const int *blk) {
+        CHK(ensure(c, s.buf, sizeof(unsigned) * (size_t)std::max<i64>(s.words, 1)));
+        if (s.words > 0)
+            hipLaunchKernelGGL(plsa::k_pack_entries, dim3(grid_for(c, s.words, 256)), dim3(256), 0, c->stream, ids, vals, s.words,
+                               lpn, blk, c->indptr, (int)c->n, item_start, item_end, item_row, seg, slot, s.buf.as<unsigned>(),
+                               c->pk_count.as<unsigned long long>());
+        return launch_check(c, "k_pack_entries");
+    };
+    if (seg > 0) {
+        s.words = plsa::plan::line_item_words(n_items, seg, lpn);
+        return pack(nullptr);
     }
-    return packed_finish(c, s, id_range, pack);
+    i64 n_blocks = 0;
+    return cut_items(c, c->indptr, c->n, block, s.blk, {}, &n_blocks, [&](int blocks) {
+        s.words = (i64)blocks * block;
+        return pack(s.blk.as<int>());
+    });
+}
+
+// the document pass' stream: whole documents, or the row items when the pass runs over those (ensure_ritems came first)
+int build_packed_csr(plsa_ctx *c) {
+    plsa_ctx::PackedStream &s = c->pk_csr;
+    const bool items = c->ritems.use && c->ritems.n > 0;
+    const int lpn = c->row_lpn, seg = items ? c->ritems.seg : 0;
+    const i64 bound = items ? plsa::plan::line_item_words(c->ritems.n, seg, lpn) : plsa::plan::line_doc_words_bound(c->nnz, c->n, lpn);
+    bool pack = false;
+    CHK(packed_begin(c, s, c->m, bound, &pack));
+    if (pack)
+        CHK(write_packed(c, s, c->col, c->val, lpn, seg, c->ritems.n, items ? c->ritems.start.as<int>() : nullptr, nullptr,
+                         items ? c->ritems.row.as<int>() : nullptr));
+    return packed_finish(c, s, c->m, pack);
+}
+
+// the column pass' stream over the column items of a built CSC copy; packed_begin came first (`pack`)
+int write_packed_csc(plsa_ctx *c, bool pack) {
+    if (!pack) return 0;
+    return write_packed(c, c->pk_csc, c->csc.row.as<int>(), c->csc.val.as<float>(), c->lpn, c->csc.seg, c->csc.n_items,
+                        c->csc.item_start.as<int>(), c->csc.item_end.as<int>(), nullptr);
+}
+i64 packed_csc_words(const plsa_ctx *c, i64 n_items_bound) { return plsa::plan::line_item_words(n_items_bound, c->csc.seg, c->lpn); }
+
+int build_packed_csc(plsa_ctx *c) {
+    bool pack = false;
+    CHK(packed_begin(c, c->pk_csc, c->n, packed_csc_words(c, c->csc.n_items), &pack));
+    CHK(write_packed_csc(c, pack));
+    return packed_finish(c, c->pk_csc, c->n, pack);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -216,8 +266,8 @@ int build_packed(plsa_ctx *c, plsa_ctx::PackedStream &s, const int *ids, const f
 // then item ids; tmp2: the items' sort keys and the sorted keys
 // ---------------------------------------------------------------------------------------------
 // entries in column order: a stable sort of the entry positions by column (within a column entries stay in document order),
-// column pointers, then one gather that also writes the column pass' packed stream (documents are its ids) when `pack`
-int csc_order_entries(plsa_ctx *c, bool pack) {
+// column pointers, then the gather
+int csc_order_entries(plsa_ctx *c) {
     plsa_ctx::Csc &s = c->csc;
     const i64 nnz = c->nnz, m = c->m;
     if (nnz <= 0) {
@@ -234,8 +284,7 @@ int csc_order_entries(plsa_ctx *c, bool pack) {
     hipLaunchKernelGGL(plsa::k_colptr_from_sorted, dim3((unsigned)((m + 256) / 256)), dim3(256), 0, c->stream,
                        c->tmp0.as<int>(), nnz, (int)m, s.colptr.as<int>());
     hipLaunchKernelGGL(plsa::k_csc_gather, dim3(grid_for(c, nnz, 256)), dim3(256), 0, c->stream,
-                       s.pos.as<int>(), c->rowidx.ids.as<int>(), c->val, nnz, s.row.as<int>(), s.val.as<float>(),
-                       pack ? c->pk_csc.buf.as<unsigned>() : nullptr, pack ? c->pk_count.as<unsigned long long>() : nullptr);
+                       s.pos.as<int>(), c->rowidx.ids.as<int>(), c->val, nnz, s.row.as<int>(), s.val.as<float>());
     return launch_check(c, "k_csc_gather");
 }
 
@@ -297,7 +346,10 @@ int csc_heavy_list(plsa_ctx *c) {
 }
 
 int ensure_csc(plsa_ctx *c) {
-    if (c->csc.valid) return 0;
+    if (c->csc.valid) {       // the copy outlived a change of lane shape (set_shape): its stream is written for the new one
+        if (!c->pk_csc.valid && c->pk_csc.reshape) CHK(build_packed_csc(c));
+        return 0;
+    }
     CHK(ensure_rowidx(c));
     c->csc.seg = plsa::plan::col_item_len(c->nnz, c->prop.multiProcessorCount, c->lpn, c->seg_override);
     const i64 nnz = c->nnz, m = c->m;
@@ -307,10 +359,13 @@ int ensure_csc(plsa_ctx *c) {
     CHK(ensure(c, c->csc.pos, sizeof(int) * (size_t)nnz));
     CHK(ensure(c, c->tmp0, sizeof(int) * (size_t)std::max<i64>(nnz, m + 1)));  // counts, then sorted keys
     CHK(ensure(c, c->tmp1, sizeof(int) * (size_t)nnz));                         // iota
+    // the column pass' packed stream is written with the copy, over its items (documents are its ids).  Every column wastes
+    // less than one item: nnz / seg + m bounds the item count before the cut
     bool pack = false;
-    CHK(packed_begin(c, c->pk_csc, c->n, &pack));
-    CHK(csc_order_entries(c, pack));
+    CHK(packed_begin(c, c->pk_csc, c->n, packed_csc_words(c, nnz / std::max(c->csc.seg, 1) + m), &pack));
+    CHK(csc_order_entries(c));
     CHK(csc_items_in_visiting_order(c));
+    CHK(write_packed_csc(c, pack));
     CHK(csc_item_records(c));
     CHK(csc_heavy_list(c));
     if (!pack) HIPCHK(c, hipStreamSynchronize(c->stream));      // (a written stream: packed_finish waits, for n_heavy too)
@@ -319,10 +374,15 @@ int ensure_csc(plsa_ctx *c) {
     return 0;
 }
 
-// the document pass' packed stream: built on the first fused pass after an upload / bootstrap / generate
+// the document pass' packed stream: built on the first fused pass after an upload / bootstrap / generate, and again when the
+// document pass' lane count or its row items are no longer what the layout was written for
 int ensure_packed_csr(plsa_ctx *c) {
-    if (!c->packed || c->pk_csr.valid) return 0;
-    return build_packed(c, c->pk_csr, c->col, c->val, c->m);
+    if (!c->packed) return 0;
+    CHK(ensure_ritems(c));
+    const int seg = c->ritems.use && c->ritems.n > 0 ? c->ritems.seg : 0;
+    // (an ineligible stream, ok == false, has no layout: it stays decided until the next invalidation)
+    if (c->pk_csr.valid && (!c->pk_csr.ok || (c->pk_csr.lpn == c->row_lpn && c->pk_csr.seg == seg))) return 0;
+    return build_packed_csr(c);
 }
 
 // the column pass' packed stream: written by ensure_csc; rebuilt from the CSC arrays after plsa_release_scratch, for a fused
@@ -330,7 +390,7 @@ int ensure_packed_csr(plsa_ctx *c) {
 int ensure_packed_csc(plsa_ctx *c) {
     CHK(ensure_csc(c));
     if (!c->packed || c->pk_csc.valid) return 0;
-    return build_packed(c, c->pk_csc, c->csc.row.as<int>(), c->csc.val.as<float>(), c->n);
+    return build_packed_csc(c);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -871,11 +871,11 @@ int main(int argc, char **argv) {
     };
     if (want("row")) {
         report("k_row_pass<fused> (shipped)", time_ms([&] {
-            hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col, d_val, (int)n,
+            hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col, d_val, (const int *)nullptr, (int)n,
                                d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll,
                                (const int *)nullptr, (const int *)nullptr, 64, (i64)0, (float *)nullptr); }));
         report("k_row_pass<fused,LL> (shipped)", time_ms([&] {
-            hipLaunchKernelGGL((plsa::k_row_pass<S, false, true>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col, d_val, (int)n,
+            hipLaunchKernelGGL((plsa::k_row_pass<S, false, true>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col, d_val, (const int *)nullptr, (int)n,
                                d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll,
                                (const int *)nullptr, (const int *)nullptr, 64, (i64)0, (float *)nullptr); }));
 #define ROWV(MODE, UNR, NAME) report(NAME, time_ms([&] { hipLaunchKernelGGL((k_row_variant<MODE, UNR>), dim3(grid_row), dim3(256), 0, g_stream, \
@@ -1358,7 +1358,7 @@ int main(int argc, char **argv) {
         std::vector<int> by_len(m);
         std::iota(by_len.begin(), by_len.end(), 0);
         std::stable_sort(by_len.begin(), by_len.end(), [&](int a, int b) { return colptr[a + 1] - colptr[a] > colptr[b + 1] - colptr[b]; });
-        const double base = time_ms([&] { hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col, d_val, (int)n, d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll, (const int *)nullptr, (const int *)nullptr, 0, (i64)0, (float *)nullptr); });
+        const double base = time_ms([&] { hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col, d_val, (const int *)nullptr, (int)n, d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll, (const int *)nullptr, (const int *)nullptr, 0, (i64)0, (float *)nullptr); });
         printf("{\"test\": \"row_hot\", \"variant\": \"shipped k_row_pass<fused>\", \"ms\": %.4f}\n", base);
         fflush(stdout);
         for (int R : {0, 64, 128, 256, 512}) {
@@ -1408,7 +1408,7 @@ int main(int argc, char **argv) {
                 std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return ip[a + 1] - ip[a] > ip[b + 1] - ip[b]; });
                 int *d_ip = dev(ip), *d_cc = dev(cc), *d_ord = dev(ord);
                 float *d_vv = dev(vv);
-                const double shipped = time_ms([&] { hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_ip, d_cc, d_vv, (int)n, d_ord, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll, (const int *)nullptr, (const int *)nullptr, 0, (i64)0, (float *)nullptr); });
+                const double shipped = time_ms([&] { hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_ip, d_cc, d_vv, (const int *)nullptr, (int)n, d_ord, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll, (const int *)nullptr, (const int *)nullptr, 0, (i64)0, (float *)nullptr); });
                 const double full = time_ms([&] { hipLaunchKernelGGL((k_row_variant<0, 4>), dim3(grid_row), dim3(256), 0, g_stream, d_ip, d_cc, d_vv, (int)n, d_ord, d_U, d_Vt, d_Un, thresh); });
                 const double gath = time_ms([&] { hipLaunchKernelGGL((k_row_variant<2, 4>), dim3(grid_row), dim3(256), 0, g_stream, d_ip, d_cc, d_vv, (int)n, d_ord, d_U, d_Vt, d_Un, thresh); });
                 printf("{\"test\": \"row_cold\", \"head_words\": %d, \"part\": \"%s\", \"entries\": %lld, \"share_of_nnz\": %.3f, \"ms_shipped_kernel\": %.4f, \"ms_variant\": %.4f, \"ms_gather_only\": %.4f}\n",
@@ -1436,7 +1436,7 @@ int main(int argc, char **argv) {
         const int grid82 = (int)std::min<i64>((n + 31) / 32, grid_cap);
         for (int mp = 0; mp < 3; ++mp) {
             const int *cc = maps[mp];
-            const double full = time_ms([&] { hipLaunchKernelGGL((plsa::k_row_pass<S82, false, false, false>), dim3(grid82), dim3(256), 0, g_stream, d_indptr, cc, d_val, (int)n, d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll, (const int *)nullptr, (const int *)nullptr, 0, (i64)0, (float *)nullptr); });
+            const double full = time_ms([&] { hipLaunchKernelGGL((plsa::k_row_pass<S82, false, false, false>), dim3(grid82), dim3(256), 0, g_stream, d_indptr, cc, d_val, (const int *)nullptr, (int)n, d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll, (const int *)nullptr, (const int *)nullptr, 0, (i64)0, (float *)nullptr); });
             const double gath = time_ms([&] { hipLaunchKernelGGL((k_row_variant<2, 4>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, cc, d_val, (int)n, d_order, d_U, d_Vt, d_Un, thresh); });
             printf("{\"test\": \"row_hitmiss\", \"row_map\": \"%s\", \"ms_shipped_kernel\": %.4f, \"ms_gather_only_probe_variant\": %.4f, \"rows_per_ns_shipped\": %.1f}\n",
                    map_name[mp], full, gath, nnz / full / 1e6);
@@ -1530,7 +1530,7 @@ int main(int argc, char **argv) {
                 const double b = time_ms([&] { hipLaunchKernelGGL((k_row_variant<2, 4>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col2, d_val2, (int)n, d_order, d_U, d_Vt, d_Un, thresh); });
                 const double c8 = time_ms([&] { hipLaunchKernelGGL((k_row_variant<0, 8>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col2, d_val2, (int)n, d_order, d_U, d_Vt, d_Un, thresh); });
                 const double s1 = time_ms([&] {
-                    hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col2, d_val2, (int)n,
+                    hipLaunchKernelGGL((plsa::k_row_pass<S, false, false>), dim3(grid_row), dim3(256), 0, g_stream, d_indptr, d_col2, d_val2, (const int *)nullptr, (int)n,
                                d_order, d_U, d_Vt, (const float *)nullptr, d_Un, (const float *)nullptr, (float *)nullptr, 64, thresh, d_ll,
                                (const int *)nullptr, (const int *)nullptr, 64, (i64)0, (float *)nullptr); });
                 printf("{\"test\": \"row_entry_order\", \"order\": \"%s\", \"rep\": %d, \"full_unr4_ms\": %.4f, \"gather_only_unr4_ms\": %.4f, \"full_unr8_ms\": %.4f, \"shipped_ms\": %.4f}\n", nm, rep, a, b, c8, s1);
