@@ -8,7 +8,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from .engine import arithmetic_flags, default_flags
+from .engine import PLSA_FUSED, PLSA_REFERENCE_LL, PLSA_REFERENCE_SUMS, arithmetic_flags, default_flags
 from .utils import normalize
 
 DEVICE_INIT_MIN_CELLS = 262_144        # factor cells from which ENSTOP_AMD_HOST_INIT=auto initialises on the device
@@ -29,6 +29,31 @@ def effective_weights(sample_weight):
     weights as float32.  Callers that cast first (the *_inner functions) hand in the cast array."""
     weighted = sample_weight is not None and np.any(np.asarray(sample_weight) != 1.0)
     return np.asarray(sample_weight, np.float32) if weighted else None
+
+
+def resolve_smoothing(name, value):
+    """A pseudo-count of smoothed EM (smoothed.py) as a float: None is 0.0 (off); anything that is not a finite number >= 0
+    is a ValueError that names the parameter.  Called before an engine is touched."""
+    if value is None:
+        return 0.0
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be None or a finite number >= 0, not %r" % (name, value)) from None
+    if not (v >= 0.0 and np.isfinite(v)) or isinstance(value, (bool, np.bool_)):
+        raise ValueError("%s must be None or a finite number >= 0, not %r" % (name, value))
+    return v
+
+
+def smoothed_flags(flags):
+    """The flag bits of a smoothed fit, refused where smoothed EM has no form: it runs the fused schedule in the default
+    arithmetic only."""
+    flags = resolve_flags(flags)
+    if not flags & PLSA_FUSED:
+        raise ValueError("smoothed EM runs the fused schedule only (ENSTOP_AMD_MATERIALISE / flags without PLSA_FUSED)")
+    if flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL):
+        raise ValueError("smoothed EM has no form in the reference arithmetic (ENSTOP_AMD_ARITHMETIC / flags=%d)" % flags)
+    return flags
 
 
 def device_init_wanted(cells):

@@ -108,6 +108,12 @@ SIGNATURES = {
                                                  C.c_double, C.POINTER(_i64)]),
     "plsa_synthetic_dominant_topics": (C.c_int, [_ctx, _i32p]),
     "plsa_temper_factors": (C.c_int, [_ctx, C.c_double, _vp, _vp]),
+    # smoothed (MAP) EM: declared in plsa_hip_diag.h, in a section of its own
+    "plsa_fit_smoothed": (C.c_int, [_ctx, _vp, C.c_double, C.c_double, _i32, _i32, C.c_double, C.c_float, _i32, C.POINTER(_i32),
+                                    _vp, C.POINTER(_i32)]),
+    "plsa_refit_smoothed": (C.c_int, [_ctx, _vp, C.c_double, _i32, _i32, C.c_double, C.c_float, _i32, C.POINTER(_i32), _vp,
+                                      C.POINTER(_i32)]),
+    "plsa_log_posterior": (C.c_int, [_ctx, _vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
 }
 
 # include/plsa_hip_members.h: batched ensemble members (a table of its own: SIGNATURES is the two headers above, exactly)

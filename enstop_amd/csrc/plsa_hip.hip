@@ -287,6 +287,10 @@ struct plsa_ctx {
         i64 snap_n = 0, snap_m = 0;
         int snap_k = 0;
     } tempered;
+    // smoothed EM (plsa_smoothed.hpp): norm_pdz [n] of the document pass in flight, which k_smooth_rows reads right behind it
+    // (nothing else ever does: no validity to keep), the slab partials [2][256] of k_log_prior, its two sums and the page-locked
+    // slot they are copied to.  Kept between calls, freed by plsa_release_scratch
+    struct Smoothed { DevBuf norm_pdz, partials, out; Pinned<double> h_out; } smoothed;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -976,15 +980,8 @@ int run_col_pass(plsa_ctx *c, bool from_p, const float *d_sw, float thresh, int 
     return 0;
 }
 
-// Vacc -> normalised topics in Vt[1-cv]  (plsa.py:196-199)
-int run_v_normalise(plsa_ctx *c) {
-    if (c->sharded && c->comm) {
-        // doc-sharded fit: the un-normalised P(w|z) sums of the local rows become the global sums (the
-        // `.sum(axis=0)` over tiles of distributed_plsa.py:116-128 / block_parallel_plsa.py:182-185) --
-        // in place, on the stream this chain runs on (underneath the document pass when overlapped)
-        Scope s(c, "rccl_allreduce_accumulator");
-        NCCLCHK(c, ncclAllReduce(c->Vacc.p, c->Vacc.p, (size_t)c->m * c->kp, ncclFloat, ncclSum, c->comm, c->ls));
-    }
+// norm_pwz[z] = sum_w Vacc[w, z]: float64 slab sums, added in a fixed order
+int run_vacc_norm(plsa_ctx *c) {
     const int nb = (int)std::min<i64>(plsa::NORM_BLOCKS, std::max<i64>(1, c->m));
     CHK(ensure(c, c->colsum_partials, sizeof(double) * (size_t)nb * c->kp));
     {
@@ -998,6 +995,19 @@ int run_v_normalise(plsa_ctx *c) {
         hipLaunchKernelGGL(plsa::k_colsum_final, dim3(1), dim3(256), 0, c->ls,
                            c->colsum_partials.as<double>(), nb, c->kp, c->norm_pwz.as<float>());
     }
+    return 0;                        // (the caller's launch_check covers both)
+}
+
+// Vacc -> normalised topics in Vt[1-cv]  (plsa.py:196-199)
+int run_v_normalise(plsa_ctx *c) {
+    if (c->sharded && c->comm) {
+        // doc-sharded fit: the un-normalised P(w|z) sums of the local rows become the global sums (the
+        // `.sum(axis=0)` over tiles of distributed_plsa.py:116-128 / block_parallel_plsa.py:182-185) --
+        // in place, on the stream this chain runs on (underneath the document pass when overlapped)
+        Scope s(c, "rccl_allreduce_accumulator");
+        NCCLCHK(c, ncclAllReduce(c->Vacc.p, c->Vacc.p, (size_t)c->m * c->kp, ncclFloat, ncclSum, c->comm, c->ls));
+    }
+    CHK(run_vacc_norm(c));
     {
         Scope s(c, "k_v_normalise");
         const i64 total4 = c->m * c->kp / 4;
@@ -1755,9 +1765,11 @@ int plsa_release_scratch(plsa_ctx *c) {
                       // re-created by the next plsa_stack_reserve / plsa_comm_allgather_stack
                       &c->comm_stack, &c->comm_recv, &c->comm_send, &c->metric_mask, &c->metric_small,
                       &c->score.indptr, &c->score.col, &c->score.val, &c->score.flag, &c->score.out,
-                      &c->tempered.U, &c->tempered.Vt, &c->tempered.snapU, &c->tempered.snapVt})
+                      &c->tempered.U, &c->tempered.Vt, &c->tempered.snapU, &c->tempered.snapVt,
+                      &c->smoothed.norm_pdz, &c->smoothed.partials, &c->smoothed.out})
         b->release();
     c->tempered.have_snap = false;
+    c->smoothed.h_out.reset();           // (the stream is idle: nothing is on its way there)
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
     // gather that needs a larger one, or plsa_destroy.
@@ -2299,3 +2311,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_tempered.hpp"           // ... and the loop, the snapshot slot and the diagnostic read-back
 #include "plsa_online_kernels.hpp"     // online (stepwise) EM (include/plsa_hip_online.h): the blend of the statistic ...
 #include "plsa_online.hpp"             // ... and the state, the step and the fold
+#include "plsa_smoothed_kernels.hpp"   // smoothed (MAP) EM (plsa_hip_diag.h): pseudo-counts behind the passes, the log prior ...
+#include "plsa_smoothed.hpp"           // ... and the two loops and the objective

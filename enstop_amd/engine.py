@@ -416,6 +416,33 @@ class Engine:
         self._ok(self._L.plsa_factors_restore(self._h))
         return self
 
+    # -- smoothed (MAP) EM (include/plsa_hip_diag.h, its own section) ----------------------------------
+    def fit_smoothed(self, doc_topic_smoothing=0.0, topic_word_smoothing=0.0, sample_weight=None, n_iter=100,
+                     n_iter_per_test=10, tolerance=0.001, e_step_thresh=1e-32, flags=None, trace=False):
+        """fit() with the pseudo-counts a = doc_topic_smoothing and b = topic_word_smoothing added to the expected counts of
+        every M-step: P(z|d) = (n_dz + a) / (N_d + k a), P(w|z) = (n_wz + b) / (N_z + m b).  Same loop, stop rule and return
+        values as fit; the trace holds the log posterior (log_posterior) where fit has the log-likelihood.  a == b == 0 is
+        fit().  Fused default arithmetic on one GPU only: anything else is a DeviceError that launches nothing."""
+        def fn(h, sw, *rest):
+            return self._L.plsa_fit_smoothed(h, sw, float(doc_topic_smoothing), float(topic_word_smoothing), *rest)
+        return self._drive(fn, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace)
+
+    def refit_smoothed(self, doc_topic_smoothing=0.0, sample_weight=None, n_iter=50, n_iter_per_test=10, tolerance=0.005,
+                       e_step_thresh=1e-32, flags=None, trace=False):
+        """refit() with the document-side pseudo-count: only P(z|d) moves, the topics are never written.  0 is refit()."""
+        def fn(h, sw, *rest):
+            return self._L.plsa_refit_smoothed(h, sw, float(doc_topic_smoothing), *rest)
+        return self._drive(fn, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh, flags, trace)
+
+    def log_posterior(self, sample_weight=None, doc_topic_smoothing=0.0, topic_word_smoothing=0.0):
+        """log_likelihood + a sum_d sw_d sum_z log P(z|d) + b sum_z sum_w log P(w|z) of the factors in force (float64): the
+        objective a smoothed iteration does not decrease.  At a == b == 0 it has the bits of log_likelihood."""
+        sw = None if sample_weight is None else _f32(sample_weight)
+        out = C.c_double(0.0)
+        self._ok(self._L.plsa_log_posterior(self._h, ptr(sw), float(doc_topic_smoothing), float(topic_word_smoothing),
+                                            C.byref(out)))
+        return out.value
+
     # -- doc-sharded fit building blocks ---------------------------------------------------------------
     def em_accumulate(self, sample_weight=None, e_step_thresh=1e-32, want_ll=False, materialised=False):
         """materialised: the reference's kernel sequence over this context's rows (E-step into P(z|w,d), M-step from it)

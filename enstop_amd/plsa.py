@@ -21,8 +21,8 @@ from scipy.sparse import csr_matrix, issparse
 from sklearn.base import BaseEstimator, TransformerMixin
 from sklearn.utils import check_array, check_random_state
 
-from ._driver import (effective_weights, init_factors, init_refit_factors, resolve_flags, scoped_arithmetic,
-                      scoped_p_budget)
+from ._driver import (effective_weights, init_factors, init_refit_factors, resolve_flags, resolve_smoothing,
+                      scoped_arithmetic, scoped_p_budget, smoothed_flags)
 from .engine import PLSA_FUSED, PLSA_SW_LL_ONLY, PLSA_STOP_NO_ZERO_ARM, arithmetic_flags, get_engine
 from .utils import (_check_sample_weight, coherence, log_lift, mean_coherence, mean_log_lift, normalize,
                     standardize_input)
@@ -278,11 +278,17 @@ def plsa_refit(X, topics, sample_weight, n_iter=50, n_iter_per_test=10, toleranc
 
 
 def _refit_on_engine(eng, X, topics, sample_weight, n_iter, n_iter_per_test, tolerance, e_step_thresh, rng, flags=None,
-                     trace=False, p_budget=None):
+                     trace=False, p_budget=None, doc_topic_smoothing=0.0):
     """plsa_refit's body on `eng`, whose lock the caller holds: X becomes the resident corpus, P(z|d) is drawn from `rng`
-    and folded in against the fixed `topics`, and both stay on the device (scoring.held_out_scores goes on from there)."""
+    and folded in against the fixed `topics`, and both stay on the device (scoring.held_out_scores goes on from there).
+    doc_topic_smoothing > 0: the fold-in of a smoothed model (Engine.refit_smoothed), same start, same loop."""
+    if doc_topic_smoothing:
+        flags = smoothed_flags(flags)            # a ValueError before the engine is touched
     eng.upload_csr(X)
     init_refit_factors(eng, X.shape[0], topics, rng)
+    if doc_topic_smoothing:
+        return eng.refit_smoothed(doc_topic_smoothing, effective_weights(sample_weight), n_iter, n_iter_per_test, tolerance,
+                                  e_step_thresh, flags, trace=trace)
     with scoped_p_budget(eng, p_budget):
         return eng.refit(effective_weights(sample_weight), n_iter, n_iter_per_test, tolerance, e_step_thresh, flags,
                          trace=trace)
@@ -324,6 +330,11 @@ class _ScoringMixin:
         # same entry order directly (and, unlike a COO -> CSR round trip, never merges duplicates)
         X = csr_matrix(X) if not issparse(X) else X.tocsr()
         # plsa.py:1210-1218: fixed n_iter=50, n_iter_per_test=5, tolerance=0.001
+        a = self._smoothing()[0] if hasattr(self, "_smoothing") else 0.0
+        if a:                                    # a model fitted with doc_topic_smoothing folds in with it
+            from .smoothed import plsa_refit_smoothed
+            return plsa_refit_smoothed(X, self.components_, sample_weight, a, n_iter=50, n_iter_per_test=5, tolerance=0.001,
+                                       random_state=random_state, device=self.device, flags=self._flags())
         return plsa_refit(X, self.components_, sample_weight, n_iter=50, n_iter_per_test=5, tolerance=0.001,
                           random_state=random_state, device=self.device,
                           flags=self._flags() if hasattr(self, "_flags") else None, p_budget=getattr(self, "p_budget", None))
@@ -334,7 +345,8 @@ class _ScoringMixin:
         flags = self._flags() if hasattr(self, "_flags") else None
         return held_out_scores(X, self.components_, method=method, fraction=fraction,
                                random_state=self.transform_random_seed, n_iter=50, n_iter_per_test=5, tolerance=0.001,
-                               device=self.device, flags=flags, on_zero=on_zero)
+                               device=self.device, flags=flags, on_zero=on_zero,
+                               doc_topic_smoothing=self._smoothing()[0] if hasattr(self, "_smoothing") else 0.0)
 
     def score_samples(self, X):
         """log P(document) [n] of every document of X under its OWN fold-in: P(z|d) is fitted on the very tokens that are
@@ -367,6 +379,12 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
     (0, 1] fits all of X at that fixed beta.  Sets `beta_`, `n_iter_`, `validation_perplexity_`, `tempering_report_`.
     Default arithmetic only; the other estimators of this module refuse it.
 
+    `doc_topic_smoothing`, `topic_word_smoothing` (additive; None: off, nothing changes): the pseudo-counts a, b >= 0 of MAP
+    EM under Dirichlet priors (enstop_amd.smoothed): P(z|d) = (n_dz + a) / (N_d + k a), P(w|z) = (n_wz + b) / (N_z + m b).
+    With topic_word_smoothing > 0 no entry of `components_` is 0, so held-out text with unseen words has a finite
+    perplexity; a model fitted with doc_topic_smoothing folds in with it (transform, score_samples, perplexity).  Default
+    arithmetic only, not together with `tempering`; the other estimators of this module refuse them.
+
     `p_budget`: bytes that P(z|w,d) may take in fit / transform with `arithmetic="reference"` (plsa_fit; None: the
     ENSTOP_AMD_P_BUDGET_MB environment variable, unset: no budget); no effect outside the reference arithmetic.
 
@@ -377,8 +395,11 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
 
     def __init__(self, n_components=10, init="random", n_iter=100, n_iter_per_test=10,
                  tolerance=0.001, e_step_thresh=1e-32, transform_random_seed=42, random_state=None,
-                 device=None, arithmetic=None, p_budget=None, tempering=None):
+                 device=None, arithmetic=None, p_budget=None, tempering=None, doc_topic_smoothing=None,
+                 topic_word_smoothing=None):
         self.n_components = n_components
+        self.doc_topic_smoothing = doc_topic_smoothing
+        self.topic_word_smoothing = topic_word_smoothing
         self.arithmetic = arithmetic
         self.p_budget = p_budget
         self.tempering = tempering
@@ -394,27 +415,53 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
     _extra_flags = 0      # subclasses: stop-test variant of the reference module they stand in for
     _base_flags = None    # None: default_flags(), the environment consulted (StreamedPLSA: its own base)
     tempering = None      # (class default: estimators unpickled from before the parameter existed, and the subclasses)
+    doc_topic_smoothing = None
+    topic_word_smoothing = None
+    _OPTIONAL = ("tempering", "doc_topic_smoothing", "topic_word_smoothing")
 
     def _flags(self):
         # arithmetic="reference": the reference's float32 sums, rounding for rounding (engine.arithmetic_flags)
         return resolve_flags(None, getattr(self, "arithmetic", None), self._extra_flags, self._base_flags)
 
-    # `tempering` is listed among the parameters only while it is set: the parameter lists of existing pipelines, grids and
-    # pickles are what they were, and clone() still carries a value that was given
+    # `tempering` and the two smoothing parameters are listed among the parameters only while they are set: the parameter
+    # lists of existing pipelines, grids and pickles are what they were, and clone() still carries a value that was given
     def get_params(self, deep=True):
         params = super().get_params(deep)
-        if params.get("tempering", None) is None:
-            params.pop("tempering", None)
+        for name in self._OPTIONAL:
+            if params.get(name, None) is None:
+                params.pop(name, None)
         return params
 
     def set_params(self, **params):
-        if "tempering" in params:
-            self.tempering = params.pop("tempering")
+        for name in self._OPTIONAL:
+            if name in params:
+                setattr(self, name, params.pop(name))
         return super().set_params(**params) if params else self
+
+    def _smoothing(self):
+        """(a, b) of smoothed EM, (0.0, 0.0) while neither parameter is set; every refusal is a ValueError raised here,
+        before an engine is touched"""
+        given = [name for name in ("doc_topic_smoothing", "topic_word_smoothing") if getattr(self, name, None) is not None]
+        if not given:
+            return 0.0, 0.0
+        if type(self) is not PLSA:
+            raise ValueError("%s is offered by PLSA only, not by %s" % (given[0], type(self).__name__))
+        if getattr(self, "tempering", None) is not None:
+            raise ValueError("%s and tempering=%r do not combine" % (given[0], self.tempering))
+        if arithmetic_flags(getattr(self, "arithmetic", None)):
+            raise ValueError("%s has no form in the reference arithmetic (arithmetic=%r)" % (given[0], self.arithmetic))
+        return (resolve_smoothing("doc_topic_smoothing", self.doc_topic_smoothing),
+                resolve_smoothing("topic_word_smoothing", self.topic_word_smoothing))
 
     def _fit_factors(self, X, sample_weight):
         if getattr(self, "tempering", None) is not None:
             return self._fit_factors_tempered(X, sample_weight)
+        if any(getattr(self, name, None) is not None for name in ("doc_topic_smoothing", "topic_word_smoothing")):
+            from .smoothed import plsa_fit_smoothed
+            a, b = self._smoothing()
+            return plsa_fit_smoothed(X, self.n_components, sample_weight, a, b, self.init, self.n_iter, self.n_iter_per_test,
+                                     self.tolerance, self.e_step_thresh, self.random_state, device=self.device,
+                                     flags=self._flags(), return_info=True)
         return plsa_fit(X, self.n_components, sample_weight, self.init, self.n_iter, self.n_iter_per_test,
                         self.tolerance, self.e_step_thresh, self.random_state, device=self.device,
                         flags=self._flags(), return_info=True, p_budget=getattr(self, "p_budget", None))
@@ -450,6 +497,7 @@ class PLSA(_TopicMetricsMixin, _ScoringMixin, BaseEstimator, TransformerMixin):
         return self
 
     def fit_transform(self, X, y=None, sample_weight=None):
+        self._smoothing()
         X = check_array(X, accept_sparse="csr")
         X = standardize_input(X)
         if not issparse(X):

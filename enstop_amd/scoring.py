@@ -16,6 +16,7 @@ import numpy as np
 from scipy.sparse import csr_matrix, issparse
 from sklearn.utils import check_random_state
 
+from ._driver import resolve_smoothing, smoothed_flags
 from .engine import get_engine
 from .plsa import _refit_on_engine
 
@@ -67,7 +68,7 @@ def document_log_likelihood(X, doc_topics, topics, sample_weight=None, device=No
 
 
 def held_out_scores(X, topics, method="completion", fraction=0.5, random_state=42, n_iter=50, n_iter_per_test=5,
-                    tolerance=0.001, device=None, flags=None, on_zero="inf"):
+                    tolerance=0.001, device=None, flags=None, on_zero="inf", doc_topic_smoothing=0.0):
     """Scores the documents X under the fixed `topics` [k, m]; the iteration defaults are transform's.
 
     method="fold_in": refit P(z|d) on X, score X.  method="completion": split_documents(X, fraction, rng), refit on the
@@ -79,7 +80,11 @@ def held_out_scores(X, topics, method="completion", fraction=0.5, random_state=4
     is the mass on words the model gives no probability, which the other two leave out), `scored_documents` (bool [n]:
     False where the observed or the held-out part is empty -- a fold-in of nothing is undefined), `perplexity` =
     exp(-sum ll / sum tokens) over the scored documents, and `n_iter` of the fold-in.  on_zero="inf": the perplexity is
-    inf when a scored document has unscored mass; "skip": that mass is left out of both sums."""
+    inf when a scored document has unscored mass; "skip": that mass is left out of both sums.  doc_topic_smoothing: the
+    document-side pseudo-count of a smoothed model (enstop_amd.smoothed): the fold-in is then the smoothed refit."""
+    doc_topic_smoothing = resolve_smoothing("doc_topic_smoothing", doc_topic_smoothing)
+    if doc_topic_smoothing:
+        flags = smoothed_flags(flags)            # refused here, before an engine is touched
     if method not in ("completion", "fold_in"):
         raise ValueError('method must be "completion" or "fold_in", not %r' % (method,))
     if on_zero not in ("inf", "skip"):
@@ -94,7 +99,8 @@ def held_out_scores(X, topics, method="completion", fraction=0.5, random_state=4
         scored = _nonempty_rows(X)
     eng = get_engine(device)
     with eng.lock:
-        iters, _ = _refit_on_engine(eng, observed, topics, None, n_iter, n_iter_per_test, tolerance, 1e-32, rng, flags)
+        iters, _ = _refit_on_engine(eng, observed, topics, None, n_iter, n_iter_per_test, tolerance, 1e-32, rng, flags,
+                                    doc_topic_smoothing=doc_topic_smoothing)
         ll, tokens, unscored = eng.score_rows(held)
     if on_zero == "inf" and np.any(unscored[scored] > 0):
         perplexity = np.inf

@@ -147,6 +147,51 @@ int plsa_synthetic_dominant_topics(plsa_ctx *ctx, int32_t *out /* [n], host */);
  * (either may be NULL).  The factors stay as they are.  Tests need the exact bits of the tables.               */
 int plsa_temper_factors(plsa_ctx *ctx, double beta, float *U_out, float *V_out);
 
+/* ---- smoothed (MAP) EM --------------------------------------------------------------------------------
+ * Declared here because include/ is closed to new files and the feature headers to new entries; these three are an
+ * estimator, not a diagnostic, and move to a header of their own when that listing is next opened.  The reference has no
+ * counterpart.
+ *
+ * Every fit of plsa_hip.h is a maximum-likelihood fit: a word a topic never saw gets P(w|z) = 0 exactly, and exact zeros are
+ * absorbing under EM.  MAP estimation under Dirichlet priors adds a pseudo-count to every expected count before it is
+ * normalised.  a >= 0 (document side) and b >= 0 (word side) are those counts, the Dirichlet concentrations minus one.  One
+ * smoothed iteration is the ordinary E-step followed by
+ *
+ *   n_dz = sum_w x_dw P(z|w,d)            N_d = sum_z n_dz      (unweighted)        P(z|d) = (n_dz + a) / (N_d + k a)
+ *   n_wz = sum_d sw_d x_dw P(z|w,d)       N_z = sum_w n_wz      (weighted)          P(w|z) = (n_wz + b) / (N_z + m b)
+ *
+ * which is EM on the log posterior
+ *
+ *   F = sum sw_d x_dw log sum_z P(w|z) P(z|d)  +  a sum_d sw_d sum_z log P(z|d)  +  b sum_z sum_w log P(w|z) .
+ *
+ * F does not decrease from one iteration to the next; it stands in the trace and in the stop test where plsa_fit has the
+ * log-likelihood.  The fused passes are the ones plsa_fit runs: the document pass also hands back N_d, and k_smooth_rows
+ * rewrites the P(z|d) = u it has just written as fmaf(u, N_d, (float)a) / (N_d + (float)(k a)); the column pass leaves n_wz
+ * un-normalised, the existing norm kernels form N_z, and k_smooth_topics writes (n_wz + (float)b) / (float)(N_z + m b).
+ * With a = 0 the document side is plsa_fit's, launch for launch and bit for bit; with b = 0 the word side is.  A document
+ * without tokens gets 1 / k when a > 0.  The padding topics k .. kp - 1 stay exactly 0.
+ *
+ * One stream, no look-ahead buffer set, no hipGraph.  norm_pdz [n] and the partial sums of the log prior belong to the
+ * context: kept between calls, freed by plsa_release_scratch and plsa_destroy.
+ *
+ * Each of these is a status code and a message, and launches nothing: a or b negative, NaN or infinite; flags without
+ * PLSA_FUSED; flags with PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS or PLSA_REFERENCE_LL; a context in reference
+ * arithmetic (plsa_set_arithmetic), or one that is a shard of a communicator (plsa_comm_init).
+ *
+ * plsa_fit_smoothed: plsa_fit's arguments, loop and stop rule, with the pseudo-counts after sw; the trace holds F.
+ * a == 0 and b == 0 calls plsa_fit with the same arguments and does nothing else. */
+int plsa_fit_smoothed(plsa_ctx *ctx, const float *sw /* [n] or NULL */, double a, double b, int32_t n_iter, int32_t n_iter_per_test,
+                      double tolerance, float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll);
+/* plsa_refit's arguments, loop and stop rule with the document-side pseudo-count after sw: only P(z|d) moves, the topics are
+ * never written, and the trace holds F without its word-side term (a constant there).  a == 0 calls plsa_refit. */
+int plsa_refit_smoothed(plsa_ctx *ctx, const float *sw /* [n] or NULL */, double a, int32_t n_iter, int32_t n_iter_per_test,
+                        double tolerance, float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll);
+/* *out = F of the factors in force (one double).  The likelihood is plsa_log_likelihood's; each prior term is summed in float64
+ * over a fixed number of slabs of rows, so its bits do not depend on the launch geometry.  A term whose pseudo-count is 0 is
+ * neither launched nor added: at a = b = 0 the result has the bits of plsa_log_likelihood.  A factor entry equal to 0 adds
+ * nothing to a prior term (it can only stand in starting factors the caller supplied). */
+int plsa_log_posterior(plsa_ctx *ctx, const float *sw /* [n] or NULL */, double a, double b, double *out);
+
 #ifdef __cplusplus
 }
 #endif
