@@ -1,7 +1,10 @@
-// plsa_drivers.hpp -- plsa_fit and plsa_refit: the backends the loops of plsa_fit_schedule.hpp drive, and the two entry
-// points; part of plsa_hip.hip's translation unit (included at its end: it uses the context and the pass wrappers defined
-// there).  An entry point validates, sets its scopes up, builds the likelihood tests and a backend, calls the loop,
-// synchronises and reports the counts.
+// plsa_drivers.hpp -- the call frame of the fit entry points, plsa_fit and plsa_refit, and the backends the loops of
+// plsa_fit_schedule.hpp drive; part of plsa_hip.hip's translation unit (included at its end: it uses the context and the pass
+// wrappers defined there).  The frame (FitCall, fit_open, fit_run) is what plsa_fit, plsa_refit, plsa_fit_tempered,
+// plsa_fit_smoothed and plsa_refit_smoothed share: the refusals, the fit_info reset, the weights, the likelihood tests, the
+// final synchronise and the counts.  An entry point adds its eligibility, its scopes, its backend and the name of its loop.
+// Also here, for the variants included after this file: what "the plain fused schedule" means (plain_fused) and the guard
+// that stands one table in for another (StandIn).
 #pragma once
 
 #include "plsa_fit_schedule.hpp"
@@ -242,6 +245,81 @@ struct FusedFitBackend : RidingLikelihood {
     void restore() { c->cu = su; c->cv = sv; }
 };
 
+// What the variants of the fit (tempered, smoothed, online, the member batch) run: the plain fused schedule in the default
+// arithmetic.  The first reason a (context, flags) pair is not that, in the order the refusals report it.
+enum class PlainFused { OK, NOT_FUSED, FORMLESS_FLAG, REFERENCE_CONTEXT };
+
+PlainFused plain_fused(const plsa_ctx *c, int flags) {
+    if (!(flags & PLSA_FUSED)) return PlainFused::NOT_FUSED;
+    if (flags & (PLSA_SHARDED | PLSA_GRAPH | PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL)) return PlainFused::FORMLESS_FLAG;
+    return c->ref_sums || c->ref_ll ? PlainFused::REFERENCE_CONTEXT : PlainFused::OK;
+}
+
+// the refusal of a class in the word of the variant (`form`: "tempered", "smoothed", "online"); OK: 0
+int plain_fused_refusal(plsa_ctx *c, const char *who, const char *form, PlainFused cls, int flags = 0) {
+    if (cls == PlainFused::NOT_FUSED) return fail(c, "%s: %s EM runs the fused passes only (flags without PLSA_FUSED)", who, form);
+    if (cls == PlainFused::FORMLESS_FLAG)
+        return fail(c, "%s: PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS and PLSA_REFERENCE_LL have no %s form (flags=%d)", who, form, flags);
+    if (cls == PlainFused::REFERENCE_CONTEXT)
+        return fail(c, "%s: the context is in reference arithmetic (plsa_set_arithmetic), which has no %s form", who, form);
+    return 0;
+}
+
+// A stand-in table in a place the passes read (c->U[c->cu], c->Vt[c->cv]) for the length of one launch chain: the launches
+// are stream-ordered, so the pointers they were given stay valid, the buffers only change names on the host.
+struct StandIn {
+    DevBuf &place, &table;
+    StandIn(DevBuf &place_, DevBuf &table_) : place(place_), table(table_) { place.swap(table); }
+    ~StandIn() { place.swap(table); }
+};
+
+// ---- the call frame of the fit entry points ----
+struct FitCall {                     // the C arguments every one of them takes
+    const float *sw;
+    int n_iter, n_iter_per_test;
+    double tolerance;
+    int flags;
+    int32_t *iters_done;
+    float *ll_trace;
+    int32_t *n_ll;
+};
+struct FitRun {                      // what the frame hands a loop: the weights of the likelihood and of the M-step, the tests
+    const float *d_sw, *d_sw_m;
+    plsa::fit::Tests tests;
+    bool trace;
+    int iters = 0;
+};
+
+plsa::fit::Rule fit_rule(int flags) { return (flags & PLSA_STOP_NO_ZERO_ARM) ? plsa::fit::FIT_NO_ZERO_ARM : plsa::fit::FIT; }
+
+// First half: the refusals every entry point shares, then the reset of fit_info.  An entry point's eligibility and its
+// delegation come before it; its scopes (ArithmeticScope, ShardedScope) and what they refuse, between the halves.
+int fit_open(plsa_ctx *c, const char *who, const FitCall &a) {
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(need_factors(c));
+    if (a.n_iter < 0 || a.n_iter_per_test <= 0) return fail(c, "%s: bad n_iter / n_iter_per_test", who);
+    c->fit_info = plsa_ctx::FitInfo{};
+    return 0;
+}
+
+// Second half.  `loop(FitRun &)` builds the backend and calls plsa::fit::run_*: the backend is gone when it returns, so what
+// its destructor restores is in place before the synchronise, and the caller's scopes end after it.  A failing loop returns
+// at once.  plsa.py:606-628: with use_sample_weights == False the M-step ignores the weights, the log-likelihood
+// (plsa.py:591, 631) still applies them.
+template <class Loop>
+int fit_run(plsa_ctx *c, const FitCall &a, plsa::fit::Rule rule, bool fused, Loop loop) {
+    c->fit_info.fused = fused;
+    const float *d_sw = nullptr;
+    CHK(upload_sw(c, a.sw, &d_sw));
+    FitRun run{d_sw, (a.flags & PLSA_SW_LL_ONLY) ? nullptr : d_sw, {a.ll_trace, a.tolerance, rule, a.n_iter_per_test},
+               (a.flags & PLSA_TRACE_LL) != 0};
+    CHK(loop(run));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (a.iters_done) *a.iters_done = run.iters;
+    if (a.n_ll) *a.n_ll = run.tests.count;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -255,64 +333,40 @@ extern "C" {
 // pass (fit::run_fused).
 int plsa_fit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
              float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_fit: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
+    const FitCall call{sw, n_iter, n_iter_per_test, tolerance, flags, iters_done, ll_trace, n_ll};
+    CHK(fit_open(c, "plsa_fit", call));
     ArithmeticScope arithmetic_scope(c, flags);
     if ((c->ref_sums || c->ref_ll) && (flags & PLSA_SHARDED))
         return fail(c, "plsa_fit: PLSA_REFERENCE_SUMS / PLSA_REFERENCE_LL have no doc-sharded form (the reference's sums are single chains over all non-zeros)");
     // the reference arithmetic IS the reference's kernel sequence (E-step into P(z|w,d), M-step from it, likelihood): there is
     // one such arithmetic, so PLSA_FUSED has nothing to select there and is ignored
-    const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll, trace = flags & PLSA_TRACE_LL;
-    c->fit_info.fused = fused;
+    const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll;
     ShardedScope sharded_scope(c, (flags & PLSA_SHARDED) != 0);
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    // plsa.py:606-628: with use_sample_weights == False the M-step ignores the weights, the
-    // log-likelihood (plsa.py:591, 631) still applies them
-    const float *d_sw_m = (flags & PLSA_SW_LL_ONLY) ? nullptr : d_sw;
-    plsa::fit::Tests tests{ll_trace, tolerance, (flags & PLSA_STOP_NO_ZERO_ARM) ? plsa::fit::FIT_NO_ZERO_ARM : plsa::fit::FIT,
-                           n_iter_per_test};
-    int iters = 0;
-    if (!fused) {
-        MaterialisedBackend backend(c, d_sw, d_sw_m, thresh, true);
-        CHK(plsa::fit::run_materialised(backend, tests, n_iter, trace, &iters));
-    } else {
-        FusedFitBackend backend(c, d_sw, d_sw_m, thresh, flags, n_iter, n_iter_per_test);
-        CHK(plsa::fit::run_fused(backend, tests, n_iter, trace, backend.form, &iters));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = tests.count;
-    return 0;
+    return fit_run(c, call, fit_rule(flags), fused, [&](FitRun &r) {
+        if (!fused) {
+            MaterialisedBackend backend(c, r.d_sw, r.d_sw_m, thresh, true);
+            return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+        }
+        FusedFitBackend backend(c, r.d_sw, r.d_sw_m, thresh, flags, n_iter, n_iter_per_test);
+        return plsa::fit::run_fused(backend, r.tests, n_iter, r.trace, backend.form, &r.iters);
+    });
 }
 
 // plsa_refit_inner, enstop/plsa.py:884-920: topics frozen, only P(z|d) moves.
 int plsa_refit(plsa_ctx *c, const float *sw, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
                float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_refit: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
+    const FitCall call{sw, n_iter, n_iter_per_test, tolerance, flags, iters_done, ll_trace, n_ll};
+    CHK(fit_open(c, "plsa_refit", call));
     ArithmeticScope arithmetic_scope(c, flags);
-    const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll, trace = flags & PLSA_TRACE_LL;
-    c->fit_info.fused = fused;
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    plsa::fit::Tests tests{ll_trace, tolerance, plsa::fit::REFIT, n_iter_per_test};
-    int iters = 0;
-    if (!fused) {
-        MaterialisedBackend backend(c, d_sw, nullptr, thresh, false);
-        CHK(plsa::fit::run_materialised(backend, tests, n_iter, trace, &iters));
-    } else {
-        RefitBackend backend{{c, d_sw, thresh}};
-        CHK(plsa::fit::run_fused(backend, tests, n_iter, trace, plsa::fit::Form{false, false}, &iters));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = tests.count;
-    return 0;
+    const bool fused = (flags & PLSA_FUSED) && !c->ref_sums && !c->ref_ll;
+    return fit_run(c, call, plsa::fit::REFIT, fused, [&](FitRun &r) {
+        if (!fused) {
+            MaterialisedBackend backend(c, r.d_sw, nullptr, thresh, false);
+            return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+        }
+        RefitBackend backend{{c, r.d_sw, thresh}};
+        return plsa::fit::run_fused(backend, r.tests, n_iter, r.trace, plsa::fit::Form{false, false}, &r.iters);
+    });
 }
 
 }  // extern "C"

@@ -704,6 +704,13 @@ int need_factors(plsa_ctx *c) {
     return 0;
 }
 
+// how an entry point that takes weights opens when it refuses nothing in between: the device, the factors, the weights
+int open_weighted(plsa_ctx *c, const float *sw, const float **d_sw) {
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(need_factors(c));
+    return upload_sw(c, sw, d_sw);
+}
+
 // ---------------------------------------------------------------------------------------------
 // kernel wrappers
 // ---------------------------------------------------------------------------------------------
@@ -1380,10 +1387,8 @@ int plsa_set_p(plsa_ctx *c, const float *P) {
 }
 
 int plsa_m_step(plsa_ctx *c, const float *sw, int32_t update_v, float *norm_pwz, float *norm_pdz) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
     const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
+    CHK(open_weighted(c, sw, &d_sw));
     CHK(ensure(c, c->norm_pdz, sizeof(float) * (size_t)c->n));
     CHK(run_m_step_from_p(c, d_sw, update_v != 0, c->norm_pdz.as<float>()));
     if (norm_pwz && update_v)
@@ -1395,10 +1400,8 @@ int plsa_m_step(plsa_ctx *c, const float *sw, int32_t update_v, float *norm_pwz,
 }
 
 int plsa_log_likelihood(plsa_ctx *c, const float *sw, double *ll) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
     const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
+    CHK(open_weighted(c, sw, &d_sw));
     return run_loglik(c, d_sw, ll);
 }
 
@@ -2302,7 +2305,7 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 
 }  // extern "C"
 
-#include "plsa_drivers.hpp"   // plsa_fit, plsa_refit: backends of the likelihood-test loop (plsa_fit_schedule.hpp)
+#include "plsa_drivers.hpp"   // plsa_fit, plsa_refit: the call frame of the fit entry points, backends of the loop (plsa_fit_schedule.hpp)
 #include "plsa_members.hpp"   // batched ensemble members (include/plsa_hip_members.h)
 #include "plsa_nmf.hpp"       // KL-divergence NMF (include/plsa_hip_nmf.h)
 #include "plsa_score_kernels.hpp"   // held-out scoring (include/plsa_hip_score.h): the document-owned pass ...

@@ -202,7 +202,7 @@ int fit_group(plsa_members *b, const std::vector<int> &who, const std::vector<pl
     std::vector<plsa::fit::Tests> tests;
     for (int g = 0; g < G; ++g)
         tests.push_back({ll_trace ? ll_trace + (size_t)who[g] * ll_cap : nullptr, tolerance,
-                         (flags & PLSA_STOP_NO_ZERO_ARM) ? plsa::fit::FIT_NO_ZERO_ARM : plsa::fit::FIT, n_iter_per_test, ll_cap});
+                         fit_rule(flags), n_iter_per_test, ll_cap});
     std::vector<int> iters(G, 0);
     bool pending = false, first = true;
     for (int i = 0; i < n_iter && live; ++i) {
@@ -336,8 +336,7 @@ int plsa_members_fit(plsa_members *b, int32_t n_active, int32_t n_iter, int32_t 
     }
     if (n_batched) *n_batched = 0;
     // what a batch carries: the fused schedule in the engine's own arithmetic, eager, untimed, 32-bit gather tables
-    const bool call_ok = (flags & PLSA_FUSED) && !(flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL | PLSA_SHARDED | PLSA_GRAPH)) &&
-                         !L->ref_sums && !L->ref_ll && !L->graph && !L->timing && !L->row_xcd && n_iter > 0;
+    const bool call_ok = plain_fused(L, flags) == PlainFused::OK && !L->graph && !L->timing && !L->row_xcd && n_iter > 0;
     std::vector<plsa::MemberArgs> args(n_active);
     std::vector<int> key(n_active, -1);          // instantiation group: packed column stream | packed document stream
     if (call_ok)

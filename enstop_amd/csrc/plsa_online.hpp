@@ -3,7 +3,7 @@
 //
 // A plsa_online state owns the topics V [m, kp], the running statistic S [m, kp], the slab sums and the norm of the global
 // update, a step counter and ONE event.  A step runs on the block context's one stream: the state's V is swapped into the place
-// the block's passes read (c->Vt[c->cv], as TemperedInputs does it) for the length of the pass chain, then the blend, the
+// the block's passes read (c->Vt[c->cv], by a StandIn of plsa_drivers.hpp) for the length of the pass chain, then the blend, the
 // norm and the division follow on the same stream.  Steps on different contexts are ordered on the device by the event:
 // waited for by the stream at the start of a step or fold, recorded at its end.  No second stream, no look-ahead, no hipGraph.
 #pragma once
@@ -21,25 +21,12 @@ struct plsa_online {
 
 namespace {
 
-// the state's V in the place the block's passes read, for the length of one launch chain (the launches are stream-ordered:
-// the pointers they were given stay valid, the buffers only change names on the host)
-struct OnlineTopics {
-    plsa_ctx *c;
-    plsa_online *st;
-    OnlineTopics(plsa_online *st_, plsa_ctx *c_) : c(c_), st(st_) { swap(); }
-    ~OnlineTopics() { swap(); }
-    void swap() { c->Vt[c->cv].swap(st->V); }
-};
-
 size_t online_table_bytes(const plsa_online *st) { return sizeof(float) * (size_t)st->m * st->kp; }
 
 // every refusal of a step or fold that looks at the state and the block context only; launches nothing
 int online_eligible(plsa_online *st, plsa_ctx *c, const char *who, int flags) {
     if (!st) return fail(c, "%s: no state", who);
-    if (!(flags & PLSA_FUSED)) return fail(c, "%s: online EM runs the fused passes only (flags without PLSA_FUSED)", who);
-    if (flags & (PLSA_SHARDED | PLSA_GRAPH | PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL))
-        return fail(c, "%s: PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS and PLSA_REFERENCE_LL have no online form (flags=%d)", who, flags);
-    if (c->ref_sums || c->ref_ll) return fail(c, "%s: the context is in reference arithmetic (plsa_set_arithmetic), which has no online form", who);
+    CHK(plain_fused_refusal(c, who, "online", plain_fused(c, flags), flags));
     if (c->sharded || c->comm) return fail(c, "%s: the context is one shard of a communicator; online EM has no doc-sharded form", who);
     if (c->device != st->device) return fail(c, "%s: the state lives on device %d, the block context on device %d", who, st->device, c->device);
     CHK(need_factors(c));
@@ -214,7 +201,7 @@ int plsa_online_step(plsa_online *st, plsa_ctx *c, const float *sw, int32_t inne
     CHK(online_wait(st, c));
     int blocks = 0;
     {
-        OnlineTopics topics(st, c);
+        StandIn topics(c->Vt[c->cv], st->V);
         CHK(online_fold_in(c, inner_iter, d_sw, thresh));
         CHK(run_row_pass(c, false, ll_partial != nullptr, d_sw, thresh, nullptr, &blocks));
         CHK(run_col_pass(c, false, d_sw, thresh));
@@ -238,7 +225,7 @@ int plsa_online_fold(plsa_online *st, plsa_ctx *c, const float *sw, int32_t n_it
     CHK(upload_sw(c, sw, &d_sw));
     CHK(online_wait(st, c));
     {
-        OnlineTopics topics(st, c);
+        StandIn topics(c->Vt[c->cv], st->V);
         CHK(online_fold_in(c, n_iter, d_sw, thresh));
     }
     if (n_iter > 0) c->p_state.invalidate();

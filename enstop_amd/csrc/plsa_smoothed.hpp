@@ -7,7 +7,7 @@
 // run_col_pass(parts 3) leaves the un-normalised P(w|z) sums in Vacc, run_vacc_norm forms norm_pwz from them, k_smooth_topics
 // writes the new P(w|z).  A side whose pseudo-count is 0 runs the ordinary chain of that side, so it keeps its bits.  One
 // stream, no look-ahead buffers, no hipGraph; every value of the trace is k_loglik on the factors plus the log prior
-// (k_log_prior), the objective the iteration does not decrease.
+// (k_log_prior), the objective the iteration does not decrease.  The call around the loops is the frame of plsa_drivers.hpp.
 #pragma once
 
 namespace {
@@ -74,13 +74,15 @@ int run_log_posterior(plsa_ctx *c, const float *d_sw, double a, double b, double
     return 0;
 }
 
-// the reference's loop (fit::run_materialised) over smoothed iterations
+// the reference's loop (fit::run_materialised) over smoothed iterations.  update_v = false: the refit -- the document side
+// only, the topics are never written (the word-side prior is a constant there: not in F)
 struct SmoothedBackend {
     plsa_ctx *c;
     const float *d_sw, *d_sw_m;
     float thresh;
     double a, b;
-    int loglik(double *f) { return run_log_posterior(c, d_sw, a, b, f); }
+    bool update_v;
+    int loglik(double *f) { return run_log_posterior(c, d_sw, a, update_v ? b : 0.0, f); }
     int iteration() {
         float *d_norm_pdz = nullptr;
         if (a > 0.0) {
@@ -89,30 +91,15 @@ struct SmoothedBackend {
         }
         CHK(run_row_pass(c, false, false, d_sw, thresh, d_norm_pdz, nullptr));
         if (a > 0.0) CHK(run_smooth_rows(c, a));
-        if (b > 0.0) {
+        if (update_v && b > 0.0) {
             CHK(run_col_pass(c, false, d_sw_m, thresh, 3));
             CHK(run_smooth_topics(c, b));
-        } else {
+        } else if (update_v) {
             CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
             CHK(run_col_tail(c));
         }
-        c->cu ^= 1; c->cv ^= 1;
-        return 0;
-    }
-};
-
-// the refit: the document side only, the topics are never written (the word-side prior is a constant there: not in F)
-struct SmoothedRefitBackend {
-    plsa_ctx *c;
-    const float *d_sw;
-    float thresh;
-    double a;
-    int loglik(double *f) { return run_log_posterior(c, d_sw, a, 0.0, f); }
-    int iteration() {
-        CHK(ensure(c, c->smoothed.norm_pdz, sizeof(float) * (size_t)c->n));
-        CHK(run_row_pass(c, false, false, d_sw, thresh, c->smoothed.norm_pdz.as<float>(), nullptr));
-        CHK(run_smooth_rows(c, a));
         c->cu ^= 1;
+        if (update_v) c->cv ^= 1;
         return 0;
     }
 };
@@ -123,7 +110,7 @@ int smoothed_count_ok(plsa_ctx *c, const char *who, const char *name, double v) 
 }
 
 int smoothed_context_ok(plsa_ctx *c, const char *who) {
-    if (c->ref_sums || c->ref_ll) return fail(c, "%s: the context is in reference arithmetic (plsa_set_arithmetic), which has no smoothed form", who);
+    if (c->ref_sums || c->ref_ll) return plain_fused_refusal(c, who, "smoothed", PlainFused::REFERENCE_CONTEXT);
     if (c->comm) return fail(c, "%s: the context is a shard of a communicator (plsa_comm_init); smoothed EM has no multi-GPU form", who);
     return 0;
 }
@@ -131,9 +118,7 @@ int smoothed_context_ok(plsa_ctx *c, const char *who) {
 int smoothed_eligible(plsa_ctx *c, const char *who, double a, double b, int flags) {
     CHK(smoothed_count_ok(c, who, "a", a));
     CHK(smoothed_count_ok(c, who, "b", b));
-    if (!(flags & PLSA_FUSED)) return fail(c, "%s: smoothed EM runs the fused passes only (flags without PLSA_FUSED)", who);
-    if (flags & (PLSA_SHARDED | PLSA_GRAPH | PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL))
-        return fail(c, "%s: PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS and PLSA_REFERENCE_LL have no smoothed form (flags=%d)", who, flags);
+    CHK(plain_fused_refusal(c, who, "smoothed", plain_fused(c, flags), flags));
     return smoothed_context_ok(c, who);
 }
 
@@ -145,44 +130,24 @@ int plsa_fit_smoothed(plsa_ctx *c, const float *sw, double a, double b, int32_t 
                       float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
     CHK(smoothed_eligible(c, "plsa_fit_smoothed", a, b, flags));
     if (a == 0.0 && b == 0.0) return plsa_fit(c, sw, n_iter, n_iter_per_test, tolerance, thresh, flags, iters_done, ll_trace, n_ll);
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_fit_smoothed: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
-    c->fit_info.fused = 1;
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    const float *d_sw_m = (flags & PLSA_SW_LL_ONLY) ? nullptr : d_sw;
-    plsa::fit::Tests tests{ll_trace, tolerance, (flags & PLSA_STOP_NO_ZERO_ARM) ? plsa::fit::FIT_NO_ZERO_ARM : plsa::fit::FIT,
-                           n_iter_per_test};
-    int iters = 0;
-    SmoothedBackend backend{c, d_sw, d_sw_m, thresh, a, b};
-    CHK(plsa::fit::run_materialised(backend, tests, n_iter, (flags & PLSA_TRACE_LL) != 0, &iters));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = tests.count;
-    return 0;
+    const FitCall call{sw, n_iter, n_iter_per_test, tolerance, flags, iters_done, ll_trace, n_ll};
+    CHK(fit_open(c, "plsa_fit_smoothed", call));
+    return fit_run(c, call, fit_rule(flags), true, [&](FitRun &r) {
+        SmoothedBackend backend{c, r.d_sw, r.d_sw_m, thresh, a, b, true};
+        return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+    });
 }
 
 int plsa_refit_smoothed(plsa_ctx *c, const float *sw, double a, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
                         float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
     CHK(smoothed_eligible(c, "plsa_refit_smoothed", a, 0.0, flags));
     if (a == 0.0) return plsa_refit(c, sw, n_iter, n_iter_per_test, tolerance, thresh, flags, iters_done, ll_trace, n_ll);
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_refit_smoothed: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
-    c->fit_info.fused = 1;
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    plsa::fit::Tests tests{ll_trace, tolerance, plsa::fit::REFIT, n_iter_per_test};
-    int iters = 0;
-    SmoothedRefitBackend backend{c, d_sw, thresh, a};
-    CHK(plsa::fit::run_materialised(backend, tests, n_iter, (flags & PLSA_TRACE_LL) != 0, &iters));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = tests.count;
-    return 0;
+    const FitCall call{sw, n_iter, n_iter_per_test, tolerance, flags, iters_done, ll_trace, n_ll};
+    CHK(fit_open(c, "plsa_refit_smoothed", call));
+    return fit_run(c, call, plsa::fit::REFIT, true, [&](FitRun &r) {
+        SmoothedBackend backend{c, r.d_sw, nullptr, thresh, a, 0.0, false};
+        return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+    });
 }
 
 int plsa_log_posterior(plsa_ctx *c, const float *sw, double a, double b, double *out) {
@@ -190,10 +155,8 @@ int plsa_log_posterior(plsa_ctx *c, const float *sw, double a, double b, double 
     CHK(smoothed_count_ok(c, "plsa_log_posterior", "b", b));
     CHK(smoothed_context_ok(c, "plsa_log_posterior"));
     if (!out) return fail(c, "plsa_log_posterior: out is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
     const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
+    CHK(open_weighted(c, sw, &d_sw));
     return run_log_posterior(c, d_sw, a, b, out);
 }
 

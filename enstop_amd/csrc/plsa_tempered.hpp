@@ -4,8 +4,9 @@
 // A tempered iteration raises the current factors to the power beta into two side tables (k_temper), then runs the launch
 // chain of an unsharded fused iteration -- run_row_pass, run_col_pass, run_col_tail, untouched -- with the side tables standing
 // in for the current factors: the passes read c->U[c->cu] and c->Vt[c->cv], so the side tables are swapped into those two
-// places for the length of the chain (TemperedInputs) and the passes write the alternates as they always do.  One stream, no
-// look-ahead buffers, no hipGraph; every likelihood is k_loglik on the true factors.
+// places for the length of the chain (StandIn) and the passes write the alternates as they always do.  One stream, no
+// look-ahead buffers, no hipGraph; every likelihood is k_loglik on the true factors.  The call around the loop is the frame
+// of plsa_drivers.hpp.
 #pragma once
 
 namespace {
@@ -27,15 +28,6 @@ int run_temper(plsa_ctx *c, double beta) {
     return launch_check(c, "k_temper");
 }
 
-// the side tables in the places the passes read, for the length of one launch chain (the launches are stream-ordered: the
-// pointers they were given stay valid, the buffers only change names on the host)
-struct TemperedInputs {
-    plsa_ctx *c;
-    explicit TemperedInputs(plsa_ctx *c_) : c(c_) { swap(); }
-    ~TemperedInputs() { swap(); }
-    void swap() { c->U[c->cu].swap(c->tempered.U); c->Vt[c->cv].swap(c->tempered.Vt); }
-};
-
 // the reference's loop (fit::run_materialised) over tempered iterations
 struct TemperedBackend {
     plsa_ctx *c;
@@ -46,7 +38,7 @@ struct TemperedBackend {
     int iteration() {
         CHK(run_temper(c, beta));
         {
-            TemperedInputs inputs(c);
+            StandIn u(c->U[c->cu], c->tempered.U), v(c->Vt[c->cv], c->tempered.Vt);
             CHK(run_row_pass(c, false, false, d_sw, thresh, nullptr, nullptr));
             CHK(run_col_pass(c, false, d_sw_m, thresh, 1));
             CHK(run_col_tail(c));
@@ -58,11 +50,7 @@ struct TemperedBackend {
 
 int tempered_eligible(plsa_ctx *c, const char *who, double beta, int flags) {
     if (!(beta > 0.0 && beta <= 1.0)) return fail(c, "%s: beta=%g outside (0, 1]", who, beta);
-    if (!(flags & PLSA_FUSED)) return fail(c, "%s: tempered EM runs the fused passes only (flags without PLSA_FUSED)", who);
-    if (flags & (PLSA_SHARDED | PLSA_GRAPH | PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL))
-        return fail(c, "%s: PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS and PLSA_REFERENCE_LL have no tempered form (flags=%d)", who, flags);
-    if (c->ref_sums || c->ref_ll) return fail(c, "%s: the context is in reference arithmetic (plsa_set_arithmetic), which has no tempered form", who);
-    return 0;
+    return plain_fused_refusal(c, who, "tempered", plain_fused(c, flags), flags);
 }
 
 }  // namespace
@@ -73,23 +61,12 @@ int plsa_fit_tempered(plsa_ctx *c, const float *sw, double beta, int32_t n_iter,
                       float thresh, int32_t flags, int32_t *iters_done, float *ll_trace, int32_t *n_ll) {
     CHK(tempered_eligible(c, "plsa_fit_tempered", beta, flags));
     if (beta == 1.0) return plsa_fit(c, sw, n_iter, n_iter_per_test, tolerance, thresh, flags, iters_done, ll_trace, n_ll);
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(need_factors(c));
-    if (n_iter < 0 || n_iter_per_test <= 0) return fail(c, "plsa_fit_tempered: bad n_iter / n_iter_per_test");
-    c->fit_info = plsa_ctx::FitInfo{};
-    c->fit_info.fused = 1;
-    const float *d_sw = nullptr;
-    CHK(upload_sw(c, sw, &d_sw));
-    const float *d_sw_m = (flags & PLSA_SW_LL_ONLY) ? nullptr : d_sw;
-    plsa::fit::Tests tests{ll_trace, tolerance, (flags & PLSA_STOP_NO_ZERO_ARM) ? plsa::fit::FIT_NO_ZERO_ARM : plsa::fit::FIT,
-                           n_iter_per_test};
-    int iters = 0;
-    TemperedBackend backend{c, d_sw, d_sw_m, thresh, beta};
-    CHK(plsa::fit::run_materialised(backend, tests, n_iter, (flags & PLSA_TRACE_LL) != 0, &iters));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (iters_done) *iters_done = iters;
-    if (n_ll) *n_ll = tests.count;
-    return 0;
+    const FitCall call{sw, n_iter, n_iter_per_test, tolerance, flags, iters_done, ll_trace, n_ll};
+    CHK(fit_open(c, "plsa_fit_tempered", call));
+    return fit_run(c, call, fit_rule(flags), true, [&](FitRun &r) {
+        TemperedBackend backend{c, r.d_sw, r.d_sw_m, thresh, beta};
+        return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+    });
 }
 
 int plsa_factors_snapshot(plsa_ctx *c) {
@@ -130,7 +107,7 @@ int plsa_temper_factors(plsa_ctx *c, double beta, float *U_out, float *V_out) {
     CHK(need_factors(c));
     CHK(run_temper(c, beta));
     {
-        TemperedInputs inputs(c);        // the read-back of the current factors, pointed at the side tables
+        StandIn u(c->U[c->cu], c->tempered.U), v(c->Vt[c->cv], c->tempered.Vt);   // the read-back, pointed at the side tables
         CHK(plsa_get_factors(c, U_out, V_out));
     }
     return 0;
