@@ -15,6 +15,7 @@ from .sharded import sharded_plsa_fit
 from .scoring import held_out_scores, document_log_likelihood, split_documents
 from .tempered import TemperingSchedule, plsa_fit_tempered
 from .smoothed import plsa_fit_smoothed, plsa_refit_smoothed
+from .lda import LDA, lda_fit, lda_transform
 from .online import OnlinePLSA, OnlineSchedule, OnlineState, plsa_fit_online
 from .engine import Engine, DeviceError, PLSA_FUSED, PLSA_REFERENCE_SUMS, PLSA_REFERENCE_LL
 from .utils import log_lift, mean_log_lift, coherence, mean_coherence
@@ -22,5 +23,5 @@ from . import comm, distributed, engine       # enstop_amd.distributed.init() wo
 
 __all__ = ["PLSA", "StreamedPLSA", "BlockParallelPLSA", "GPUPLSA", "DistributedPLSA", "log_lift", "mean_log_lift", "coherence", "mean_coherence", "plsa_fit", "plsa_refit", "plsa_fit_inner", "plsa_refit_inner", "plsa_init",
            "plsa_e_step", "plsa_m_step", "plsa_m_step_w_sample_weight", "plsa_refit_m_step",
-           "log_likelihood", "plsa_topics", "nmf_topics", "nmf_fit", "nmf_refit", "ensemble_of_topics", "EnsembleTopics", "ensemble_fit", "sharded_plsa_fit", "held_out_scores", "document_log_likelihood", "split_documents", "TemperingSchedule", "plsa_fit_tempered", "OnlinePLSA", "OnlineSchedule", "OnlineState", "plsa_fit_online", "plsa_fit_smoothed", "plsa_refit_smoothed", "Engine", "DeviceError",
+           "log_likelihood", "plsa_topics", "nmf_topics", "nmf_fit", "nmf_refit", "ensemble_of_topics", "EnsembleTopics", "ensemble_fit", "sharded_plsa_fit", "held_out_scores", "document_log_likelihood", "split_documents", "TemperingSchedule", "plsa_fit_tempered", "OnlinePLSA", "OnlineSchedule", "OnlineState", "plsa_fit_online", "plsa_fit_smoothed", "plsa_refit_smoothed", "LDA", "lda_fit", "lda_transform", "Engine", "DeviceError",
            "PLSA_FUSED", "PLSA_REFERENCE_SUMS", "PLSA_REFERENCE_LL"]

@@ -114,6 +114,13 @@ SIGNATURES = {
     "plsa_refit_smoothed": (C.c_int, [_ctx, _vp, C.c_double, _i32, _i32, C.c_double, C.c_float, _i32, C.POINTER(_i32), _vp,
                                       C.POINTER(_i32)]),
     "plsa_log_posterior": (C.c_int, [_ctx, _vp, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    # variational Bayes LDA: declared in plsa_hip_diag.h, in a section of its own as well
+    "plsa_lda_fit": (C.c_int, [_ctx, C.c_double, C.c_double, _i32, _i32, C.c_double, _i32, C.c_float, _i32, C.POINTER(_i32), _vp,
+                               C.POINTER(_i32)]),
+    "plsa_lda_refit": (C.c_int, [_ctx, C.c_double, _i32, _i32, C.c_double, _i32, C.c_float, _i32, C.POINTER(_i32), _vp,
+                                 C.POINTER(_i32)]),
+    "plsa_lda_bound": (C.c_int, [_ctx, C.c_double, C.c_double, _i32, C.POINTER(C.c_double)]),
+    "plsa_lda_tables": (C.c_int, [_ctx, _vp, _vp]),
 }
 
 # include/plsa_hip_members.h: batched ensemble members (a table of its own: SIGNATURES is the two headers above, exactly)

@@ -291,6 +291,11 @@ struct plsa_ctx {
     // (nothing else ever does: no validity to keep), the slab partials [2][256] of k_log_prior, its two sums and the page-locked
     // slot they are copied to.  Kept between calls, freed by plsa_release_scratch
     struct Smoothed { DevBuf norm_pdz, partials, out; Pinned<double> h_out; } smoothed;
+    // variational Bayes LDA (plsa_lda.hpp): the exp-digamma side tables A [n, kp] and B [m, kp] of the state in force (valid
+    // only inside the call that formed them), the float64 sums S_d, psi(S_d) [n] and S_z, psi(S_z) [kp] they were formed with,
+    // norm_pdz [n] of the document pass in flight, the slab partials [2][256] of k_lda_bound, its two sums and the page-locked
+    // slot they are copied to.  Kept between calls, freed by plsa_release_scratch
+    struct Lda { DevBuf A, B, sums, norm_pdz, partials, out; Pinned<double> h_out; bool a_valid = false, b_valid = false; } lda;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -1769,10 +1774,13 @@ int plsa_release_scratch(plsa_ctx *c) {
                       &c->comm_stack, &c->comm_recv, &c->comm_send, &c->metric_mask, &c->metric_small,
                       &c->score.indptr, &c->score.col, &c->score.val, &c->score.flag, &c->score.out,
                       &c->tempered.U, &c->tempered.Vt, &c->tempered.snapU, &c->tempered.snapVt,
-                      &c->smoothed.norm_pdz, &c->smoothed.partials, &c->smoothed.out})
+                      &c->smoothed.norm_pdz, &c->smoothed.partials, &c->smoothed.out,
+                      &c->lda.A, &c->lda.B, &c->lda.sums, &c->lda.norm_pdz, &c->lda.partials, &c->lda.out})
         b->release();
     c->tempered.have_snap = false;
     c->smoothed.h_out.reset();           // (the stream is idle: nothing is on its way there)
+    c->lda.h_out.reset();
+    c->lda.a_valid = c->lda.b_valid = false;
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
     // gather that needs a larger one, or plsa_destroy.
@@ -2316,3 +2324,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_online.hpp"             // ... and the state, the step and the fold
 #include "plsa_smoothed_kernels.hpp"   // smoothed (MAP) EM (plsa_hip_diag.h): pseudo-counts behind the passes, the log prior ...
 #include "plsa_smoothed.hpp"           // ... and the two loops and the objective
+#include "plsa_lda_kernels.hpp"        // variational Bayes LDA (plsa_hip_diag.h): exp-digamma tables, priors behind the passes, the bound ...
+#include "plsa_lda.hpp"                // ... and the two loops, the bound and the diagnostic read-back

@@ -1,0 +1,288 @@
+// plsa_lda.hpp -- host side of variational Bayes LDA: plsa_lda_fit, plsa_lda_refit, plsa_lda_bound and plsa_lda_tables
+// (include/plsa_hip_diag.h); part of plsa_hip.hip's translation unit (included at its end: it uses the
+// context, the pass wrappers and the call frame of plsa_drivers.hpp).
+//
+// The state lives in the factor buffers: gamma [n, kp] in U[cu], lambda [m, kp] in Vt[cv].  An iteration forms the two
+// exp-digamma tables A, B into side tables of the context (every document's row of A and every word's row of B scaled to a
+// largest entry of 1, which leaves the responsibilities as they are and keeps the tables inside float32), runs the launch chain of an unsharded fused iteration with the side
+// tables standing in for the factors (StandIn) -- run_row_pass handing norm_pdz back, run_col_pass(parts 3) leaving the raw
+// counts in Vacc -- and adds the priors behind the passes (k_lda_rows, k_lda_topics).  Both updates come from the same
+// responsibilities, so the bound (run_lda_bound) never decreases.  One stream, no look-ahead buffers, no hipGraph.
+#pragma once
+
+namespace {
+
+// the float64 side arrays of the tables in force: per document S_d, psi(S_d) and the shift of its row of A; per topic S_z and
+// psi(S_z); per word the shift of its row of B
+enum LdaSum { LDA_S_DOC, LDA_PSI_DOC, LDA_SHIFT_DOC, LDA_S_TOPIC, LDA_PSI_TOPIC, LDA_SHIFT_WORD };
+
+double *lda_sums(plsa_ctx *c, LdaSum which) {
+    const size_t n = (size_t)c->n, kp = (size_t)c->kp;
+    const size_t at[6] = {0, n, 2 * n, 3 * n, 3 * n + kp, 3 * n + 2 * kp};
+    return c->lda.sums.as<double>() + at[which];
+}
+
+int lda_ensure_sums(plsa_ctx *c) {
+    return ensure(c, c->lda.sums, sizeof(double) * (3 * (size_t)c->n + 2 * (size_t)c->kp + (size_t)c->m));
+}
+
+// A <- exp(psi(gamma) - psi(S_d) - shift_d) from U[cu], shift_d the logarithm of the largest entry of document d's row (scaled;
+// otherwise no shift: the tables of the definition, for plsa_lda_tables), with S_d, psi(S_d) and shift_d left in the context
+int run_lda_table_u(plsa_ctx *c, bool scaled = true) {
+    plsa_ctx::Lda &l = c->lda;
+    if (l.a_valid && scaled) return 0;
+    l.a_valid = false;
+    CHK(ensure(c, l.A, sizeof(float) * (size_t)c->n * c->kp));
+    CHK(lda_ensure_sums(c));
+    const int kq = c->kp / 4, lanes = plsa::plan::lda_row_lanes(kq);
+    const i64 n4 = c->n * kq;
+    {
+        Scope s(c, "k_lda_rowsum");
+        hipLaunchKernelGGL(plsa::k_lda_rowsum, dim3(plsa::plan::lda_rowsum_grid(c->n, kq, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0,
+                           c->ls, c->U[c->cu].as<float4>(), (long long)c->n, kq, c->k, lanes, lda_sums(c, LDA_S_DOC),
+                           lda_sums(c, LDA_PSI_DOC), lda_sums(c, LDA_SHIFT_DOC));
+    }
+    {
+        Scope s(c, "k_lda_tables");
+        hipLaunchKernelGGL(plsa::k_lda_tables<true>, dim3(plsa::plan::lda_grid(n4, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                           c->U[c->cu].as<float4>(), l.A.as<float4>(), (long long)n4, kq, c->k, lda_sums(c, LDA_S_DOC),
+                           lda_sums(c, LDA_PSI_DOC), scaled ? lda_sums(c, LDA_SHIFT_DOC) : nullptr);
+    }
+    CHK(launch_check(c, "k_lda_tables"));
+    l.a_valid = scaled;
+    return 0;
+}
+
+// B <- exp(psi(lambda) - psi(S_z) - shift_w) from Vt[cv]: S_z from float64 slab sums (k_lda_topic_partial) added in slab order,
+// shift_w the logarithm of the largest entry of word w's row
+int run_lda_table_v(plsa_ctx *c, bool scaled = true) {
+    plsa_ctx::Lda &l = c->lda;
+    if (l.b_valid && scaled) return 0;
+    l.b_valid = false;
+    CHK(ensure(c, l.B, sizeof(float) * (size_t)c->m * c->kp));
+    CHK(lda_ensure_sums(c));
+    const int kq = c->kp / 4, lanes = plsa::plan::lda_row_lanes(kq);
+    const i64 n4 = c->m * kq;
+    const int nb = plsa::plan::lda_bound_grid(c->m);
+    CHK(ensure(c, c->colsum_partials, sizeof(double) * (size_t)nb * c->kp));
+    {
+        Scope s(c, "k_lda_topic_partial");
+        hipLaunchKernelGGL(plsa::k_lda_topic_partial, dim3(nb), dim3(plsa::plan::LDA_BLOCK), 0, c->ls, c->Vt[c->cv].as<float>(),
+                           (long long)c->m, c->kp, c->colsum_partials.as<double>());
+    }
+    {
+        Scope s(c, "k_lda_topic_sums");
+        hipLaunchKernelGGL(plsa::k_lda_topic_sums, dim3(plsa::plan::lda_topic_grid(c->kp)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                           c->colsum_partials.as<double>(), nb, c->kp, c->k, lda_sums(c, LDA_S_TOPIC), lda_sums(c, LDA_PSI_TOPIC));
+    }
+    if (scaled) {
+        Scope s(c, "k_lda_wordmax");
+        hipLaunchKernelGGL(plsa::k_lda_wordmax, dim3(plsa::plan::lda_rowsum_grid(c->m, kq, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0,
+                           c->ls, c->Vt[c->cv].as<float4>(), (long long)c->m, kq, c->k, lanes, lda_sums(c, LDA_S_TOPIC),
+                           lda_sums(c, LDA_PSI_TOPIC), lda_sums(c, LDA_SHIFT_WORD));
+    }
+    {
+        Scope s(c, "k_lda_tables");
+        hipLaunchKernelGGL(plsa::k_lda_tables<false>, dim3(plsa::plan::lda_grid(n4, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                           c->Vt[c->cv].as<float4>(), l.B.as<float4>(), (long long)n4, kq, c->k, lda_sums(c, LDA_S_TOPIC),
+                           lda_sums(c, LDA_PSI_TOPIC), scaled ? lda_sums(c, LDA_SHIFT_WORD) : nullptr);
+    }
+    CHK(launch_check(c, "k_lda_tables"));
+    l.b_valid = scaled;
+    return 0;
+}
+
+// U[out_u] <- U[out_u] * N_d + alpha behind a document pass that left N_d in c->lda.norm_pdz
+int run_lda_rows(plsa_ctx *c, double alpha) {
+    const int kq = c->kp / 4;
+    const i64 n4 = c->n * kq;
+    Scope s(c, "k_lda_rows");
+    hipLaunchKernelGGL(plsa::k_lda_rows, dim3(plsa::plan::lda_grid(n4, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                       c->U[out_u(c)].as<float4>(), c->lda.norm_pdz.as<float>(), (long long)n4, kq, c->k, (float)alpha);
+    return launch_check(c, "k_lda_rows");
+}
+
+// Vt[out_v] <- Vacc + eta behind run_col_pass(parts 3)
+int run_lda_topics(plsa_ctx *c, double eta) {
+    const int kq = c->kp / 4;
+    const i64 n4 = c->m * kq;
+    Scope s(c, "k_lda_topics");
+    hipLaunchKernelGGL(plsa::k_lda_topics, dim3(plsa::plan::lda_grid(n4, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                       c->Vacc.as<float4>(), c->Vt[out_v(c)].as<float4>(), (long long)n4, kq, c->k, (float)eta);
+    return launch_check(c, "k_lda_topics");
+}
+
+// c->lda.out[slot] <- the Dirichlet part of the bound of one table (without its constants): one partial per slab, added in order
+template <bool BY_ROW>
+int run_lda_dirichlet(plsa_ctx *c, const DevBuf &table, i64 rows, double prior, int slot) {
+    plsa_ctx::Lda &l = c->lda;
+    const int slabs = plsa::plan::lda_bound_grid(rows);
+    double *partials = l.partials.as<double>() + (size_t)slot * plsa::plan::PRIOR_SLABS;
+    {
+        Scope s(c, "k_lda_bound");
+        hipLaunchKernelGGL(plsa::k_lda_bound<BY_ROW>, dim3(slabs), dim3(plsa::plan::LDA_BLOCK), 0, c->stream, table.as<float4>(),
+                           (long long)rows, c->kp / 4, c->k, prior, lda_sums(c, BY_ROW ? LDA_S_DOC : LDA_S_TOPIC),
+                           lda_sums(c, BY_ROW ? LDA_PSI_DOC : LDA_PSI_TOPIC), partials);
+    }
+    {
+        Scope s(c, "k_ll_final");
+        hipLaunchKernelGGL(plsa::k_ll_final, dim3(1), dim3(256), 0, c->stream, partials, slabs, l.out.as<double>() + slot);
+    }
+    return launch_check(c, "k_lda_bound");
+}
+
+// c->lda.out[2] <- sum x_dw (shift_d + shift_w): what the scaling of the tables took out of the likelihood term
+int run_lda_shift_sum(plsa_ctx *c) {
+    plsa_ctx::Lda &l = c->lda;
+    const int slabs = plsa::plan::lda_shift_grid(c->n);
+    double *partials = l.partials.as<double>() + (size_t)2 * plsa::plan::PRIOR_SLABS;
+    {
+        Scope s(c, "k_lda_shift_sum");
+        hipLaunchKernelGGL(plsa::k_lda_shift_sum, dim3(slabs), dim3(plsa::plan::LDA_BLOCK), 0, c->stream, c->indptr, c->col, c->val,
+                           (long long)c->n, lda_sums(c, LDA_SHIFT_DOC), lda_sums(c, LDA_SHIFT_WORD), partials);
+    }
+    {
+        Scope s(c, "k_ll_final");
+        hipLaunchKernelGGL(plsa::k_ll_final, dim3(1), dim3(256), 0, c->stream, partials, slabs, l.out.as<double>() + 2);
+    }
+    return launch_check(c, "k_lda_shift_sum");
+}
+
+// L = sum x_dw log sum_z A_dz B_zw + the Dirichlet part of gamma (+ the Dirichlet part of lambda: with_topics) of the state in
+// force.  The likelihood term is k_loglik on the scaled tables plus the shifts the scaling took out; the constants
+// lgamma(k alpha) - k lgamma(alpha) per document and lgamma(m eta) - m lgamma(eta) per topic are added here
+int run_lda_bound(plsa_ctx *c, double alpha, double eta, bool with_topics, double *out) {
+    plsa_ctx::Lda &l = c->lda;
+    // the sums land in a page-locked slot of the context: a copy still on its way writes to memory that outlives the call
+    if (!l.h_out && host_alloc(l.h_out, 3) != hipSuccess) return fail(c, "plsa_lda_bound: page-locked buffer allocation failed");
+    double *part = l.h_out.get();
+    CHK(ensure(c, l.partials, sizeof(double) * (2 * plsa::plan::PRIOR_SLABS + plsa::plan::LDA_SHIFT_SLABS)));
+    CHK(ensure(c, l.out, sizeof(double) * 3));
+    CHK(run_lda_table_u(c));
+    CHK(run_lda_table_v(c));
+    CHK(run_lda_dirichlet<true>(c, c->U[c->cu], c->n, alpha, 0));
+    if (with_topics) CHK(run_lda_dirichlet<false>(c, c->Vt[c->cv], c->m, eta, 1));
+    CHK(run_lda_shift_sum(c));
+    HIPCHK(c, hipMemcpyAsync(part, l.out.as<double>(), sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+    double ll = 0.0;
+    {
+        StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
+        CHK(run_loglik(c, nullptr, &ll));    // waits for c->stream: the other sums have arrived as well
+    }
+    ll += part[2];
+    ll += part[0] + (double)c->n * (lgamma(c->k * alpha) - c->k * lgamma(alpha));
+    if (with_topics) ll += part[1] + (double)c->k * (lgamma((double)c->m * eta) - (double)c->m * lgamma(eta));
+    *out = ll;
+    return 0;
+}
+
+// the reference's loop (fit::run_materialised) over LDA iterations.  update_v = false: the refit -- gamma only, lambda is never
+// written and its part of the bound, a constant there, is left out
+struct LdaBackend {
+    plsa_ctx *c;
+    float thresh;
+    double alpha, eta;
+    int doc_iter;
+    bool update_v;
+    int loglik(double *f) { return run_lda_bound(c, alpha, eta, update_v, f); }
+    // gamma <- alpha + the document pass's counts under the tables in force; with_topics: lambda <- eta + the column pass's
+    // counts under the same tables
+    int round(bool with_topics) {
+        plsa_ctx::Lda &l = c->lda;
+        CHK(run_lda_table_u(c));
+        CHK(run_lda_table_v(c));
+        CHK(ensure(c, l.norm_pdz, sizeof(float) * (size_t)c->n));
+        {
+            StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
+            CHK(run_row_pass(c, false, false, nullptr, thresh, l.norm_pdz.as<float>(), nullptr));
+            if (with_topics) CHK(run_col_pass(c, false, nullptr, thresh, 3));
+        }
+        CHK(run_lda_rows(c, alpha));
+        if (with_topics) CHK(run_lda_topics(c, eta));
+        c->cu ^= 1;
+        l.a_valid = false;
+        if (with_topics) { c->cv ^= 1; l.b_valid = false; }
+        return 0;
+    }
+    int iteration() {
+        for (int r = 1; r < doc_iter; ++r) CHK(round(false));
+        return round(update_v);
+    }
+};
+
+int lda_prior_ok(plsa_ctx *c, const char *who, const char *name, double v) {
+    if (!(v > 0.0) || !std::isfinite(v)) return fail(c, "%s: prior %s=%g is not a finite number > 0", who, name, v);
+    return 0;
+}
+
+int lda_context_ok(plsa_ctx *c, const char *who) {
+    if (c->ref_sums || c->ref_ll) return plain_fused_refusal(c, who, "LDA", PlainFused::REFERENCE_CONTEXT);
+    if (c->comm) return fail(c, "%s: the context is a shard of a communicator (plsa_comm_init); LDA has no multi-GPU form", who);
+    return 0;
+}
+
+int lda_eligible(plsa_ctx *c, const char *who, double alpha, double eta, int doc_iter, int flags) {
+    CHK(lda_prior_ok(c, who, "alpha", alpha));
+    CHK(lda_prior_ok(c, who, "eta", eta));
+    if (doc_iter < 1) return fail(c, "%s: doc_iter=%d is not >= 1", who, doc_iter);
+    CHK(plain_fused_refusal(c, who, "LDA", plain_fused(c, flags), flags));
+    return lda_context_ok(c, who);
+}
+
+// the tables of a call are formed from the state the call finds: whatever an earlier call left is stale
+void lda_open(plsa_ctx *c) { c->lda.a_valid = c->lda.b_valid = false; }
+
+}  // namespace
+
+extern "C" {
+
+int plsa_lda_fit(plsa_ctx *c, double alpha, double eta, int32_t n_iter, int32_t n_iter_per_test, double tolerance, int32_t doc_iter,
+                 float thresh, int32_t flags, int32_t *iters_done, float *bound_trace, int32_t *n_bound) {
+    CHK(lda_eligible(c, "plsa_lda_fit", alpha, eta, doc_iter, flags));
+    const FitCall call{nullptr, n_iter, n_iter_per_test, tolerance, flags, iters_done, bound_trace, n_bound};
+    CHK(fit_open(c, "plsa_lda_fit", call));
+    lda_open(c);
+    return fit_run(c, call, fit_rule(flags), true, [&](FitRun &r) {
+        LdaBackend backend{c, thresh, alpha, eta, doc_iter, true};
+        return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+    });
+}
+
+int plsa_lda_refit(plsa_ctx *c, double alpha, int32_t n_iter, int32_t n_iter_per_test, double tolerance, int32_t doc_iter,
+                   float thresh, int32_t flags, int32_t *iters_done, float *bound_trace, int32_t *n_bound) {
+    CHK(lda_eligible(c, "plsa_lda_refit", alpha, 1.0, doc_iter, flags));
+    const FitCall call{nullptr, n_iter, n_iter_per_test, tolerance, flags, iters_done, bound_trace, n_bound};
+    CHK(fit_open(c, "plsa_lda_refit", call));
+    lda_open(c);
+    return fit_run(c, call, plsa::fit::REFIT, true, [&](FitRun &r) {
+        LdaBackend backend{c, thresh, alpha, 1.0, doc_iter, false};
+        return plsa::fit::run_materialised(backend, r.tests, n_iter, r.trace, &r.iters);
+    });
+}
+
+int plsa_lda_bound(plsa_ctx *c, double alpha, double eta, int32_t with_topics, double *out) {
+    CHK(lda_prior_ok(c, "plsa_lda_bound", "alpha", alpha));
+    if (with_topics) CHK(lda_prior_ok(c, "plsa_lda_bound", "eta", eta));
+    CHK(lda_context_ok(c, "plsa_lda_bound"));
+    if (!out) return fail(c, "plsa_lda_bound: out is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(need_factors(c));
+    lda_open(c);
+    return run_lda_bound(c, alpha, eta, with_topics != 0, out);
+}
+
+int plsa_lda_tables(plsa_ctx *c, float *A_out, float *B_out) {
+    CHK(lda_context_ok(c, "plsa_lda_tables"));
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(need_factors(c));
+    lda_open(c);
+    CHK(run_lda_table_u(c, false));
+    CHK(run_lda_table_v(c, false));
+    {
+        StandIn u(c->U[c->cu], c->lda.A), v(c->Vt[c->cv], c->lda.B);   // the read-back, pointed at the side tables
+        CHK(plsa_get_factors(c, A_out, B_out));
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -443,6 +443,50 @@ class Engine:
                                             C.byref(out)))
         return out.value
 
+    # -- variational Bayes LDA (include/plsa_hip_diag.h, its own section) --------------------------------------------------
+    def _lda_drive(self, fn, n_iter, n_iter_per_test, tolerance, doc_iter, thresh, flags, trace):
+        bound = np.zeros(n_iter + 2, np.float32)
+        iters, count = C.c_int32(0), C.c_int32(0)
+        flags = PLSA_FUSED if flags is None else flags
+        if trace:
+            flags |= PLSA_TRACE_LL
+        self._ok(fn(int(n_iter), int(n_iter_per_test), float(tolerance), int(doc_iter), np.float32(thresh), int(flags),
+                    C.byref(iters), bound.ctypes.data, C.byref(count)))
+        return iters.value, bound[: count.value].copy()
+
+    def lda_fit(self, doc_topic_prior, topic_word_prior, n_iter=100, n_iter_per_test=10, tolerance=0.001, doc_iter=1,
+                e_step_thresh=1e-32, flags=None, trace=False):
+        """Variational Bayes LDA from the state set_factors put on the engine, gamma [n, k] where P(z|d) lives and lambda [k, m]
+        where P(w|z) lives: every iteration forms the exp-digamma tables of the state, runs the fused passes on them and
+        adds the priors behind the passes.  fit()'s loop, stop rule and return values, with the bound (lda_bound) where fit
+        has the log-likelihood.  doc_iter - 1 extra rounds per iteration update gamma alone.  Any priors > 0; fused default
+        arithmetic on one GPU only: anything else is a DeviceError that launches nothing."""
+        def fn(*rest):
+            return self._L.plsa_lda_fit(self._h, float(doc_topic_prior), float(topic_word_prior), *rest)
+        return self._lda_drive(fn, n_iter, n_iter_per_test, tolerance, doc_iter, e_step_thresh, flags, trace)
+
+    def lda_refit(self, doc_topic_prior, n_iter=50, n_iter_per_test=10, tolerance=0.005, doc_iter=1, e_step_thresh=1e-32,
+                  flags=None, trace=False):
+        """The fold-in: only gamma moves, lambda is never written; the bound of the trace leaves the topic part out."""
+        def fn(*rest):
+            return self._L.plsa_lda_refit(self._h, float(doc_topic_prior), *rest)
+        return self._lda_drive(fn, n_iter, n_iter_per_test, tolerance, doc_iter, e_step_thresh, flags, trace)
+
+    def lda_bound(self, doc_topic_prior, topic_word_prior=None):
+        """The variational bound of the state in force (float64); topic_word_prior=None leaves the topic part out."""
+        out = C.c_double(0.0)
+        eta = 1.0 if topic_word_prior is None else float(topic_word_prior)
+        self._ok(self._L.plsa_lda_bound(self._h, float(doc_topic_prior), eta, 0 if topic_word_prior is None else 1, C.byref(out)))
+        return out.value
+
+    def lda_tables(self):
+        """(A [n, k], B [k, m]): the exp-digamma tables an LDA iteration forms from the state in force, which stays as it is
+        (diagnostics / tests)."""
+        n, m, _ = self.shape
+        A, B = np.empty((n, self.k), np.float32), np.empty((self.k, m), np.float32)
+        self._ok(self._L.plsa_lda_tables(self._h, ptr(A), ptr(B)))
+        return A, B
+
     # -- doc-sharded fit building blocks ---------------------------------------------------------------
     def em_accumulate(self, sample_weight=None, e_step_thresh=1e-32, want_ll=False, materialised=False):
         """materialised: the reference's kernel sequence over this context's rows (E-step into P(z|w,d), M-step from it)

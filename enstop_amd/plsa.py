@@ -300,13 +300,17 @@ def _refit_on_engine(eng, X, topics, sample_weight, n_iter, n_iter_per_test, tol
 class _TopicMetricsMixin:
     """coherence() / log_lift() of the fitted topics, signatures as enstop/plsa.py:1222-1285."""
 
+    def _metric_topics(self):
+        """the topics the metrics score, rows that sum to 1: `components_` for the pLSA estimators"""
+        return self.components_
+
     def _metric(self, topic_num, n_words, single, mean):
         if not isinstance(topic_num, int) and topic_num is not None:
             raise ValueError("Topic number must be an integer or None.")
         if topic_num is None:
-            return mean(self.components_, self.training_data_, n_words)
+            return mean(self._metric_topics(), self.training_data_, n_words)
         if 0 <= topic_num < self.n_components:
-            return single(self.components_, topic_num, self.training_data_, n_words)
+            return single(self._metric_topics(), topic_num, self.training_data_, n_words)
         raise ValueError("Topic number must be in range 0 to {}".format(self.n_components))
 
     def coherence(self, topic_num=None, n_words=20):

@@ -192,6 +192,85 @@ int plsa_refit_smoothed(plsa_ctx *ctx, const float *sw /* [n] or NULL */, double
  * nothing to a prior term (it can only stand in starting factors the caller supplied). */
 int plsa_log_posterior(plsa_ctx *ctx, const float *sw /* [n] or NULL */, double a, double b, double *out);
 
+/*
+ * ---- variational Bayes LDA: four entry points in a section of their own, like smoothed EM above ----
+ *
+ * Latent Dirichlet allocation by batch variational Bayes (Blei, Ng, Jordan 2003; the batch form of Hoffman, Blei, Bach 2010,
+ * which scikit-learn's LatentDirichletAllocation follows).  The reference has no counterpart.
+ *
+ * The state is gamma [n, k] > 0 (the Dirichlet parameters of the document mixtures) and lambda [k, m] > 0 (those of the
+ * topics).  It lives where P(z|d) and P(w|z) live: plsa_set_factors puts a state on the context, plsa_get_factors reads it
+ * back, plsa_factors_snapshot and plsa_factors_restore work on it -- none of them normalises.  With
+ *
+ *   A_dz = exp(psi(gamma_dz) - psi(sum_z gamma_dz))          B_zw = exp(psi(lambda_zw) - psi(sum_w lambda_zw))
+ *
+ * the optimal responsibilities are phi_dwz = A_dz B_zw / sum_z' A_dz' B_z'w, and one iteration is
+ *
+ *   gamma_dz = alpha + sum_w x_dw phi_dwz                      lambda_zw = eta + sum_d x_dw phi_dwz
+ *
+ * with both sums taken under the SAME tables: given phi the bound separates in gamma and lambda, so this is exact coordinate
+ * ascent and the bound never decreases.  Any priors alpha, eta > 0 are legal, the sparse regime below 1 included, which
+ * plsa_fit_smoothed (pseudo-counts >= 0, concentrations >= 1) cannot express.
+ *
+ * The tables: every entry is evaluated in float64 (a digamma by recurrence to x >= 6 and a twelve-term asymptotic series,
+ * absolute error below 2^-40 wherever psi(x) >= -88) and rounded to float32 once.  The row sums of gamma are float64 sums of
+ * the stored float32 entries, the topic sums of lambda float64 slab sums added in slab order.
+ *
+ * float32 ends at exp(-87), and psi(0.01) is -100.6: an entry at a prior below about 0.012 is below the float32 normal range.
+ * The responsibilities do not change when a document's row of A or a word's row of B (its k entries) is multiplied by a
+ * constant, so the passes run on SCALED tables: every such row is divided by its largest entry, in the exponent
+ * (exp(psi(x) - psi(S) - shift), shift the logarithm of the row's largest entry, float64).  The largest entry of every such row is 1;
+ * an entry that still leaves float32 is below 1e-38 of the largest entry of its row and may be flushed to 0.  This holds for
+ * each table alone, NOT for the products the passes and k_loglik form: with both priors around 0.01, a token whose document
+ * peaks on one topic and whose word peaks on another can have every product A_dz B_zw below float32.  Such a token drops out of
+ * the counts and the bound is -inf: priors that small are legal, but a state that far apart is outside what float32 tables hold.  The bound's likelihood term gets sum x_dw (shift_d + shift_w) back, a float64 sum.  thresh is compared with the
+ * products of the scaled tables.  plsa_lda_tables reads the tables of the definition, unscaled.
+ *
+ * One stream, no look-ahead buffer set, no hipGraph: the launch chain of an iteration is k_lda_rowsum, k_lda_topic_partial,
+ * k_lda_topic_sums, k_lda_wordmax, k_lda_tables (twice), k_row_pass<fused>, k_col_pass<fused>, k_col_reduce, k_lda_rows and k_lda_topics on
+ * the context's stream.  The passes are the ones plsa_fit runs.
+ *
+ * The bound (what the trace holds and the stop test sees, where plsa_fit has the log-likelihood):
+ *
+ *   L = sum x_dw log sum_z A_dz B_zw
+ *     + sum_d [lgamma(k alpha) - k lgamma(alpha) - lgamma(S_d) + sum_z (lgamma(gamma_dz) + (alpha - gamma_dz)(psi(gamma_dz) - psi(S_d)))]
+ *     + sum_z [lgamma(m eta) - m lgamma(eta) - lgamma(S_z) + sum_w (lgamma(lambda_zw) + (eta - lambda_zw)(psi(lambda_zw) - psi(S_z)))]
+ *
+ * for any gamma, lambda > 0 with phi at its optimum (scikit-learn's _approx_bound).  The likelihood term is k_loglik on the
+ * scaled tables plus the shifts (k_lda_shift_sum); the Dirichlet sums and the shift sum are float64 slab partials added in a
+ * fixed order (k_lda_bound, k_ll_final), whose bits do not depend on the launch geometry.  A state entry equal to 0 adds nothing to a table or to the bound.
+ *
+ * There are no sample weights: weights made resident by plsa_set_sample_weight are not applied.
+ *
+ * Each of these is a status code and a message, and launches nothing: a prior that is not a finite number > 0 (NaN
+ * included); doc_iter < 1; flags without PLSA_FUSED; flags with PLSA_SHARDED, PLSA_GRAPH, PLSA_REFERENCE_SUMS or
+ * PLSA_REFERENCE_LL; a context in reference arithmetic (plsa_set_arithmetic); a context that is a shard of a communicator.
+ *
+ * The side tables, the sums and the bound's scratch belong to the context: 4 kp (n + m) bytes and change, kept between calls,
+ * freed by plsa_release_scratch and plsa_destroy.
+ */
+/* n_iter iterations from the state on the context, with plsa_fit's loop and stop rule on the bound: the bound of the initial
+ * state, then one after every n_iter_per_test-th iteration, the stop on its relative change against `tolerance` (0 never stops
+ * on it).  doc_iter >= 1: the first doc_iter - 1 rounds of an iteration update gamma alone against the unchanged B, the last
+ * round updates both from the same tables.  thresh: the passes' threshold on a product A_dz B_zw, as in plsa_fit.  flags:
+ * PLSA_FUSED is required; PLSA_TRACE_LL and PLSA_STOP_NO_ZERO_ARM mean what they mean in plsa_fit.  iters_done, bound_trace,
+ * n_bound: plsa_fit's iters_done, ll_trace, n_ll. */
+int plsa_lda_fit(plsa_ctx *ctx, double alpha, double eta, int32_t n_iter, int32_t n_iter_per_test, double tolerance,
+                 int32_t doc_iter, float thresh, int32_t flags, int32_t *iters_done, float *bound_trace, int32_t *n_bound);
+
+/* The fold-in: gamma alone moves, lambda is never written.  Every iteration is doc_iter gamma rounds against the B of the
+ * lambda on the context; the bound of the trace is the likelihood term and the document part (the topic part is a constant
+ * there).  Loop and stop rule of plsa_refit. */
+int plsa_lda_refit(plsa_ctx *ctx, double alpha, int32_t n_iter, int32_t n_iter_per_test, double tolerance, int32_t doc_iter,
+                   float thresh, int32_t flags, int32_t *iters_done, float *bound_trace, int32_t *n_bound);
+
+/* The bound of the state in force, float64; with_topics == 0 leaves the topic part out (eta is then not read). */
+int plsa_lda_bound(plsa_ctx *ctx, double alpha, double eta, int32_t with_topics, double *out);
+
+/* Diagnostic read-back, like plsa_temper_factors: the tables A [n, k] and B [k, m] an iteration would form from the state in
+ * force, which stays as it is.  Either pointer may be NULL. */
+int plsa_lda_tables(plsa_ctx *ctx, float *A_out, float *B_out);
+
 #ifdef __cplusplus
 }
 #endif
