@@ -17,13 +17,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plsa_combine_plan.hpp"
+
 namespace plsa {
 
 constexpr int EMBED_MAX_NEIGHBORS = 1024;          // the selected neighbours of a row are staged in LDS
 constexpr int EMBED_MAX_DIM = 8;
 constexpr int LAYOUT_LDS_BLOCK = 1024;
-constexpr int LAYOUT_EPOCH_BLOCK = 256;
-constexpr size_t LAYOUT_LDS_BYTES = 64 * 1024;     // dynamic LDS a kernel gets without an opt-in attribute
+using plan::LAYOUT_EPOCH_BLOCK;
+using plan::LAYOUT_LDS_BYTES;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // neighbours, bandwidths, membership strengths

@@ -1,6 +1,7 @@
 // plsa_hip.hip -- host side of libplsa_hip.so: context, HBM layout, kernel dispatch, EM drivers and
-// the C ABI declared in include/plsa_hip.h (the drop-in), include/plsa_hip_diag.h (diagnostics, measurement, test
-// plumbing) and include/plsa_hip_members.h (batched ensemble members: csrc/plsa_members.hpp).  gfx950 only; no other back-end exists.
+// the C ABI declared in include/plsa_hip.h (the drop-in) and include/plsa_hip_diag.h (diagnostics, measurement, test plumbing).
+// The features built on them are host headers included at the end of this file, each after its kernel header: from the fit
+// drivers (csrc/plsa_drivers.hpp) to the topic combination (csrc/plsa_combine.hpp).  gfx950 only; no other back-end exists.
 //
 // HBM layout per context (n docs, m words, k topics, kp = 4*ceil(k/4)):
 //   base CSR     indptr i32[n+1], col i32[nnz], val f32[nnz]      the uploaded corpus
@@ -32,21 +33,17 @@
 #include "../../include/plsa_hip.h"
 #include "../../include/plsa_hip_diag.h"
 #include "../../include/plsa_hip_members.h"
-#include "../../include/plsa_hip_metrics.h"
 #include "../../include/plsa_hip_blocked.h"
-#include "../../include/plsa_hip_embed.h"
 #include "../../include/plsa_hip_nmf.h"
 #include "../../include/plsa_hip_score.h"
 #include "../../include/plsa_hip_tempered.h"
 #include "../../include/plsa_hip_online.h"
 #include "mt_jump.hpp"
-#include "plsa_embed_kernels.hpp"
 #include "plsa_init_kernels.hpp"
 #include "plsa_init_plan.hpp"
 #include "plsa_kernels.hpp"
 #include "plsa_launch_plan.hpp"
 #include "plsa_member_kernels.hpp"
-#include "plsa_metric_kernels.hpp"
 #include "plsa_nmf_kernels.hpp"
 #include "plsa_ref_kernels.hpp"
 #include "plsa_synth.hpp"
@@ -1853,325 +1850,6 @@ int plsa_measure_stream_bandwidth(plsa_ctx *c, int64_t bytes, int32_t kind, int3
     return 0;
 }
 
-// enstop/utils.py:22-41 with axis=1 (float64, sequential marginal, guarded division)
-void plsa_host_normalize_rows(double *a, int64_t rows, int64_t cols) {
-    for (int64_t i = 0; i < rows; ++i) {
-        double *r = a + i * cols;
-        double marginal = 0.0;
-        for (int64_t j = 0; j < cols; ++j) marginal += r[j];
-        if (marginal > 0.0)
-            for (int64_t j = 0; j < cols; ++j) r[j] /= marginal;
-    }
-}
-
-// enstop/enstop_.py:258-266 (pairwise umap.distances.hellinger over the stacked topics) on the device
-int plsa_all_pairs_hellinger(plsa_ctx *c, const float *topics, int64_t t, int64_t m, double *D) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!topics || !D || t <= 0 || m <= 0 || t > 65536) return fail(c, "plsa_all_pairs_hellinger: bad arguments");
-    const int nt = (int)((t + plsa::HELL_TILE - 1) / plsa::HELL_TILE);
-    std::vector<int> ti, tj;
-    for (int i = 0; i < nt; ++i) for (int j = i; j < nt; ++j) { ti.push_back(i); tj.push_back(j); }
-    // enough vocabulary slices to fill the chip, each a multiple of the staging step
-    int slices = (int)std::max<i64>(1, std::min<i64>(64, (4 * (i64)c->prop.multiProcessorCount + (i64)ti.size() - 1) / (i64)ti.size()));
-    // (slices * tiles <= 4 CUs + tiles: with slices > 1 the [slices][t][t] partial buffer stays below 2e8 bytes)
-    i64 slice = ((m + slices - 1) / slices + plsa::HELL_KSTEP - 1) / plsa::HELL_KSTEP * plsa::HELL_KSTEP;
-    slices = (int)((m + slice - 1) / slice);
-    DevBuf R, l1, part, dD, dt;
-    CHK(ensure(c, R, sizeof(float) * (size_t)t * m));
-    CHK(ensure(c, l1, sizeof(double) * (size_t)t));
-    CHK(ensure(c, part, sizeof(double) * (size_t)slices * t * t));
-    CHK(ensure(c, dD, sizeof(double) * (size_t)t * t));
-    CHK(ensure(c, dt, sizeof(int) * 2 * ti.size()));
-    hipError_t e = hipMemcpyAsync(R.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dt.p, ti.data(), sizeof(int) * ti.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dt.as<int>() + ti.size(), tj.data(), sizeof(int) * tj.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(plsa::k_hell_prepare, dim3((unsigned)t), dim3(256), 0, c->stream, R.as<float>(), (int)t, (i64)m, l1.as<double>());
-        { Scope s(c, "k_hell_gram");
-          hipLaunchKernelGGL(plsa::k_hell_gram, dim3((unsigned)ti.size(), (unsigned)slices), dim3(256), 0, c->stream,
-                             R.as<float>(), (int)t, (i64)m, slice, dt.as<int>(), dt.as<int>() + ti.size(), part.as<double>()); }
-        hipLaunchKernelGGL(plsa::k_hell_finish, dim3((unsigned)((t * t + 255) / 256)), dim3(256), 0, c->stream,
-                           part.as<double>(), slices, (int)t, l1.as<double>(), dD.as<double>());
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, "plsa_all_pairs_hellinger: %s", hipGetErrorString(e));
-    return 0;
-}
-
-// enstop/utils.py:150-203 (the counts behind coherence: pairwise document-list intersections, `data > 0` column sums) on
-// the device: plsa_metric_kernels.hpp
-int plsa_codocument_counts(plsa_ctx *c, const int32_t *words, int64_t sets, int32_t nw, int32_t max_sets_per_pass,
-                           int64_t *co, int64_t *positive) {
-    if (!c) return fail(c, "plsa_codocument_counts: ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (nw < 2 || nw > plsa::METRIC_MAX_WORDS)
-        return fail(c, "plsa_codocument_counts: nw=%d outside [2,%d]", nw, plsa::METRIC_MAX_WORDS);
-    if (sets < 1 || sets > ((i64)1 << 24)) return fail(c, "plsa_codocument_counts: sets=%lld outside [1,2^24]", (long long)sets);
-    if (max_sets_per_pass < 0) return fail(c, "plsa_codocument_counts: max_sets_per_pass=%d is negative", max_sets_per_pass);
-    if (!words || !co || !positive) return fail(c, "plsa_codocument_counts: words, co and positive must not be NULL");
-    if (c->n <= 0) return fail(c, "plsa_codocument_counts: no corpus uploaded");
-    // the ids index colptr on the device: checked here, before anything is launched
-    for (i64 i = 0; i < sets * nw; ++i)
-        if (words[i] < 0 || words[i] >= c->m)
-            return fail(c, "plsa_codocument_counts: word id %d (set %lld, position %lld) outside [0,%lld)", words[i],
-                        (long long)(i / nw), (long long)(i % nw), (long long)c->m);
-    const i64 n = c->n, per_co = (i64)nw * nw;
-    std::fill(co, co + sets * per_co, (int64_t)0);
-    std::fill(positive, positive + sets * nw, (int64_t)0);
-    if (c->nnz == 0) return 0;
-    CHK(ensure_csc(c));
-    // sets per pass: a quarter of what is free (the masks already held count as free), at most 4096 (grid z)
-    i64 chunk = max_sets_per_pass;
-    if (chunk == 0) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)1 << 30; }
-        chunk = (i64)((free_b + c->metric_mask.cap) / 4 / (sizeof(unsigned) * (size_t)n));
-    }
-    chunk = std::max<i64>(1, std::min<i64>(std::min<i64>(chunk, sets), 4096));
-    CHK(ensure(c, c->metric_mask, sizeof(unsigned) * (size_t)chunk * (size_t)n));
-    // [chunk][nw][nw] co-document counters, [chunk][nw] positive counters, [chunk][nw] word ids
-    const size_t co_b = sizeof(unsigned long long) * (size_t)(chunk * per_co), pos_b = sizeof(unsigned long long) * (size_t)(chunk * nw);
-    CHK(ensure(c, c->metric_small, co_b + pos_b + sizeof(int) * (size_t)(chunk * nw)));
-    unsigned long long *d_co = c->metric_small.as<unsigned long long>();
-    unsigned long long *d_pos = d_co + chunk * per_co;
-    int *d_words = reinterpret_cast<int *>(d_pos + chunk * nw);
-    // several workgroups per posting list (a head word has about n postings), several per mask row
-    const unsigned mark_x = (unsigned)std::max<i64>(1, std::min<i64>(64, (n + 4095) / 4096));
-    const unsigned count_x = (unsigned)std::max<i64>(1, std::min<i64>(128, (n + 2047) / 2048));
-    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are copied out as int64");
-    for (i64 s0 = 0; s0 < sets; s0 += chunk) {
-        const i64 cs = std::min<i64>(chunk, sets - s0);
-        HIPCHK(c, hipMemsetAsync(c->metric_mask.p, 0, sizeof(unsigned) * (size_t)cs * (size_t)n, c->stream));
-        HIPCHK(c, hipMemsetAsync(d_co, 0, co_b + pos_b, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_words, words + s0 * nw, sizeof(int) * (size_t)(cs * nw), hipMemcpyHostToDevice, c->stream));
-        { Scope s(c, "k_metric_mark");
-          hipLaunchKernelGGL(plsa::k_metric_mark, dim3(mark_x, (unsigned)nw, (unsigned)cs), dim3(plsa::METRIC_BLOCK), 0, c->stream,
-                             c->csc.colptr.as<int>(), c->csc.row.as<int>(), c->csc.val.as<float>(), d_words, (int)nw, (int64_t)n,
-                             c->metric_mask.as<unsigned>(), d_pos); }
-        CHK(launch_check(c, "k_metric_mark"));
-        { Scope s(c, "k_metric_count");
-          hipLaunchKernelGGL(plsa::k_metric_count, dim3(count_x, (unsigned)cs), dim3(plsa::METRIC_BLOCK), 0, c->stream,
-                             c->metric_mask.as<unsigned>(), (int)nw, (int64_t)n, d_co); }
-        CHK(launch_check(c, "k_metric_count"));
-        HIPCHK(c, hipMemcpyAsync(co + s0 * per_co, d_co, sizeof(int64_t) * (size_t)(cs * per_co), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(positive + s0 * nw, d_pos, sizeof(int64_t) * (size_t)(cs * nw), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // the next chunk reuses the staging buffers
-    }
-    return 0;
-}
-
-// enstop/enstop_.py:354-414 (umap.UMAP on the stacked topics): nearest neighbours, bandwidths and membership strengths of a
-// precomputed distance matrix -- plsa_embed_kernels.hpp
-int plsa_knn_membership(plsa_ctx *c, const double *D, int64_t t, int32_t n_neighbors, int32_t *idx, float *dist, float *rho,
-                        float *sigma, float *member) {
-    if (!c) return fail(c, "plsa_knn_membership: ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!D || !idx || !dist || !rho || !sigma || !member) return fail(c, "plsa_knn_membership: an array is NULL");
-    if (t < 2 || t > 65536) return fail(c, "plsa_knn_membership: t=%lld outside [2,65536]", (long long)t);
-    if (n_neighbors < 1 || n_neighbors > t || n_neighbors > plsa::EMBED_MAX_NEIGHBORS)
-        return fail(c, "plsa_knn_membership: n_neighbors=%d outside [1,min(t,%d)]", n_neighbors, plsa::EMBED_MAX_NEIGHBORS);
-    for (i64 i = 0; i < t * t; ++i)      // a NaN would never be selected: a row could run out of entries
-        if (!std::isfinite(D[i])) return fail(c, "plsa_knn_membership: D[%lld,%lld] is not finite", (long long)(i / t), (long long)(i % t));
-    const size_t tk = (size_t)t * (size_t)n_neighbors;
-    DevBuf dD, dint, dflt;
-    CHK(ensure(c, dD, sizeof(double) * (size_t)t * t));
-    CHK(ensure(c, dint, sizeof(int) * (tk + 1)));                     // idx, the arrival counter
-    CHK(ensure(c, dflt, sizeof(float) * (2 * tk + 3 * (size_t)t)));   // dist, member, rho, sigma, row sums
-    int *d_idx = dint.as<int>();
-    unsigned *d_done = reinterpret_cast<unsigned *>(d_idx + tk);
-    float *d_dist = dflt.as<float>(), *d_member = d_dist + tk, *d_rho = d_member + tk, *d_sigma = d_rho + t, *d_sum = d_sigma + t;
-    HIPCHK(c, hipMemcpyAsync(dD.p, D, sizeof(double) * (size_t)t * t, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_done, 0, sizeof(unsigned), c->stream));
-    { Scope s(c, "k_knn_membership");
-      hipLaunchKernelGGL(plsa::k_knn_membership, dim3((unsigned)t), dim3(64), 0, c->stream, dD.as<double>(), (int)t, (int)n_neighbors,
-                         d_idx, d_dist, d_rho, d_sigma, d_member, d_sum, d_done); }
-    CHK(launch_check(c, "k_knn_membership"));
-    HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * tk, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dist, d_dist, sizeof(float) * tk, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(member, d_member, sizeof(float) * tk, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(rho, d_rho, sizeof(float) * (size_t)t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sigma, d_sigma, sizeof(float) * (size_t)t, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C++" {
-namespace {
-template <int DIM>
-int layout_run(plsa_ctx *c, const plsa::LayoutGraph &G, float *y0, float *y1, bool lds, float **result) {
-    if (lds) {
-        { Scope s(c, "k_layout_lds");
-          hipLaunchKernelGGL(plsa::k_layout_lds<DIM>, dim3(1), dim3(plsa::LAYOUT_LDS_BLOCK), sizeof(float) * 2 * (size_t)G.t * DIM,
-                             c->stream, G, y0); }
-        *result = y0;
-        return launch_check(c, "k_layout_lds");
-    }
-    const unsigned grid = (unsigned)((G.t + plsa::LAYOUT_EPOCH_BLOCK - 1) / plsa::LAYOUT_EPOCH_BLOCK);
-    float *cur = y0, *nxt = y1;
-    for (int epoch = 0; epoch < G.n_epochs; ++epoch) {
-        { Scope s(c, "k_layout_epoch");
-          hipLaunchKernelGGL(plsa::k_layout_epoch<DIM>, dim3(grid), dim3(plsa::LAYOUT_EPOCH_BLOCK), 0, c->stream, G, epoch, cur, nxt); }
-        CHK(launch_check(c, "k_layout_epoch"));
-        std::swap(cur, nxt);
-    }
-    *result = cur;
-    return 0;
-}
-}  // namespace
-}  // extern "C++"
-
-// enstop/enstop_.py:354-414 (umap.UMAP on the stacked topics): the force layout of the fuzzy graph -- plsa_embed_kernels.hpp
-int plsa_layout(plsa_ctx *c, const int32_t *indptr, const int32_t *indices, const float *weights, int64_t t, int32_t dim,
-                float *y_inout, int32_t n_epochs, float a, float b, int32_t negative_sample_rate, uint64_t seed, int32_t path) {
-    if (!c) return fail(c, "plsa_layout: ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!indptr || !y_inout) return fail(c, "plsa_layout: indptr and y_inout must not be NULL");
-    if (t < 1 || t > 65536) return fail(c, "plsa_layout: t=%lld outside [1,65536]", (long long)t);
-    if (dim < 1 || dim > plsa::EMBED_MAX_DIM) return fail(c, "plsa_layout: dim=%d outside [1,%d]", dim, plsa::EMBED_MAX_DIM);
-    if (n_epochs < 1 || n_epochs > 100000) return fail(c, "plsa_layout: n_epochs=%d outside [1,100000]", n_epochs);
-    if (negative_sample_rate < 1 || negative_sample_rate > 64)
-        return fail(c, "plsa_layout: negative_sample_rate=%d outside [1,64]", negative_sample_rate);
-    if (path < 0 || path > 2) return fail(c, "plsa_layout: path=%d is none of 0 (auto), 1 (LDS), 2 (per epoch)", path);
-    if (!std::isfinite(a) || !std::isfinite(b) || a <= 0.f || b <= 0.f) return fail(c, "plsa_layout: a and b must be positive");
-    // the graph indexes the position buffers on the device: checked here, before anything is launched
-    if (indptr[0] != 0) return fail(c, "plsa_layout: indptr[0] is not 0");
-    for (i64 i = 0; i < t; ++i)
-        if (indptr[i + 1] < indptr[i]) return fail(c, "plsa_layout: indptr decreases at row %lld", (long long)i);
-    const i64 nnz = indptr[t];
-    if (nnz > 0 && (!indices || !weights)) return fail(c, "plsa_layout: indices and weights must not be NULL");
-    float wmax = 0.f;
-    for (i64 e = 0; e < nnz; ++e) {
-        if (indices[e] < 0 || indices[e] >= t) return fail(c, "plsa_layout: indices[%lld]=%d outside [0,%lld)", (long long)e, indices[e], (long long)t);
-        if (!std::isfinite(weights[e]) || !(weights[e] > 0.f)) return fail(c, "plsa_layout: weights[%lld] is not a positive number", (long long)e);
-        wmax = std::max(wmax, weights[e]);
-    }
-    for (i64 i = 0; i < t * dim; ++i)
-        if (!std::isfinite(y_inout[i])) return fail(c, "plsa_layout: y_inout[%lld] is not finite", (long long)i);
-    const size_t y_bytes = sizeof(float) * (size_t)t * (size_t)dim;
-    const bool fits = 2 * y_bytes <= plsa::LAYOUT_LDS_BYTES;
-    if (path == 1 && !fits)
-        return fail(c, "plsa_layout: path 1 keeps two position buffers in LDS: 2 * %lld * %d * 4 = %zu bytes exceed %zu", (long long)t,
-                    dim, 2 * y_bytes, plsa::LAYOUT_LDS_BYTES);
-    const bool lds = path == 1 || (path == 0 && fits);
-    // the schedule in float32, as the kernels advance it: an edge is due every max(W) / w epochs, first in that epoch
-    const float rate = (float)negative_sample_rate;
-    std::vector<float> eps((size_t)nnz);
-    std::vector<float2> state((size_t)nnz);
-    for (i64 e = 0; e < nnz; ++e) {
-        eps[e] = wmax / weights[e];
-        state[e] = make_float2(eps[e], eps[e] / rate);
-    }
-    DevBuf dptr, dind, deps, dstate, dy;
-    CHK(ensure(c, dptr, sizeof(int) * (size_t)(t + 1)));
-    CHK(ensure(c, dind, sizeof(int) * (size_t)nnz));
-    CHK(ensure(c, deps, sizeof(float) * (size_t)nnz));
-    CHK(ensure(c, dstate, sizeof(float2) * (size_t)nnz));
-    CHK(ensure(c, dy, 2 * y_bytes));
-    HIPCHK(c, hipMemcpyAsync(dptr.p, indptr, sizeof(int) * (size_t)(t + 1), hipMemcpyHostToDevice, c->stream));
-    if (nnz > 0) {
-        HIPCHK(c, hipMemcpyAsync(dind.p, indices, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(deps.p, eps.data(), sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dstate.p, state.data(), sizeof(float2) * (size_t)nnz, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(dy.p, y_inout, y_bytes, hipMemcpyHostToDevice, c->stream));
-    plsa::LayoutGraph G;
-    G.indptr = dptr.as<int>(); G.indices = dind.as<int>(); G.eps = deps.as<float>(); G.state = dstate.as<float2>();
-    G.t = (int)t; G.n_epochs = n_epochs; G.a = a; G.b = b; G.rate = rate; G.seed = seed;
-    float *y0 = dy.as<float>(), *y1 = y0 + (size_t)t * dim, *result = nullptr;
-    int rc = 1;
-    switch (dim) {
-    case 1: rc = layout_run<1>(c, G, y0, y1, lds, &result); break;
-    case 2: rc = layout_run<2>(c, G, y0, y1, lds, &result); break;
-    case 3: rc = layout_run<3>(c, G, y0, y1, lds, &result); break;
-    case 4: rc = layout_run<4>(c, G, y0, y1, lds, &result); break;
-    case 5: rc = layout_run<5>(c, G, y0, y1, lds, &result); break;
-    case 6: rc = layout_run<6>(c, G, y0, y1, lds, &result); break;
-    case 7: rc = layout_run<7>(c, G, y0, y1, lds, &result); break;
-    case 8: rc = layout_run<8>(c, G, y0, y1, lds, &result); break;
-    }
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }   // the host vectors above are still being read
-    HIPCHK(c, hipMemcpyAsync(y_inout, result, y_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// enstop/enstop_.py:244-253 (all_pairs_kl_divergence over the stacked topics) on the device
-int plsa_all_pairs_kl(plsa_ctx *c, const float *topics, int64_t t, int64_t m, double *D) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!topics || !D || t <= 0 || m <= 0 || t > 65536) return fail(c, "plsa_all_pairs_kl: bad arguments");
-    const int nt = (int)((t + plsa::HELL_TILE - 1) / plsa::HELL_TILE);
-    const i64 tiles = (i64)nt * nt;
-    int slices = (int)std::max<i64>(1, std::min<i64>(64, (4 * (i64)c->prop.multiProcessorCount + tiles - 1) / tiles));
-    i64 slice = ((m + slices - 1) / slices + plsa::HELL_KSTEP - 1) / plsa::HELL_KSTEP * plsa::HELL_KSTEP;
-    slices = (int)((m + slice - 1) / slice);
-    DevBuf T, part, dD;
-    CHK(ensure(c, T, sizeof(float) * (size_t)t * m));
-    CHK(ensure(c, part, sizeof(double) * (size_t)slices * t * t));
-    CHK(ensure(c, dD, sizeof(double) * (size_t)t * t));
-    hipError_t e = hipMemcpyAsync(T.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        { Scope s(c, "k_kl_gram");
-          hipLaunchKernelGGL(plsa::k_kl_gram, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, c->stream,
-                             T.as<float>(), (int)t, (i64)m, slice, part.as<double>()); }
-        hipLaunchKernelGGL(plsa::k_sum_slices, dim3((unsigned)((t * t + 255) / 256)), dim3(256), 0, c->stream,
-                           part.as<double>(), slices, (i64)t * t, dD.as<double>());
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(D, dD.p, sizeof(double) * (size_t)t * t, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, "plsa_all_pairs_kl: %s", hipGetErrorString(e));
-    return 0;
-}
-
-// enstop/enstop_.py:299-308, 340-345 (weights == NULL) and 385-393 (membership-strength weights)
-int plsa_cluster_representatives(plsa_ctx *c, const float *topics, int64_t t, int64_t m, const int32_t *labels,
-                                 const double *weights, int32_t n_clusters, float *out) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!topics || !labels || !out || t <= 0 || m <= 0 || n_clusters < 0)
-        return fail(c, "plsa_cluster_representatives: bad arguments");
-    if (n_clusters == 0) return 0;
-    // members of each cluster in row order (labels < 0 are noise; labels >= n_clusters are an error)
-    std::vector<int> first((size_t)n_clusters + 1, 0), members;
-    for (int64_t i = 0; i < t; ++i) {
-        if (labels[i] >= n_clusters) return fail(c, "plsa_cluster_representatives: label %d >= n_clusters %d", labels[i], n_clusters);
-        if (labels[i] >= 0) first[(size_t)labels[i] + 1]++;
-    }
-    for (int cl = 0; cl < n_clusters; ++cl) first[(size_t)cl + 1] += first[(size_t)cl];
-    members.resize((size_t)first[(size_t)n_clusters] + 1);
-    {
-        std::vector<int> fill(first.begin(), first.end() - 1);
-        for (int64_t i = 0; i < t; ++i) if (labels[i] >= 0) members[(size_t)fill[(size_t)labels[i]]++] = (int)i;
-    }
-    // enstop_.py:385-393 np.average raises on an all-zero weight vector; callers handle that case
-    const int nb = (int)((m + 255) / 256);
-    DevBuf T, dfirst, dmem, dw, rep, bs, dout;
-    CHK(ensure(c, T, sizeof(float) * (size_t)t * m));
-    CHK(ensure(c, dfirst, sizeof(int) * first.size()));
-    CHK(ensure(c, dmem, sizeof(int) * members.size()));
-    if (weights) CHK(ensure(c, dw, sizeof(double) * (size_t)t));
-    CHK(ensure(c, rep, sizeof(double) * (size_t)n_clusters * m));
-    CHK(ensure(c, bs, sizeof(double) * (size_t)n_clusters * nb));
-    CHK(ensure(c, dout, sizeof(float) * (size_t)n_clusters * m));
-    hipError_t e = hipMemcpyAsync(T.p, topics, sizeof(float) * (size_t)t * m, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dfirst.p, first.data(), sizeof(int) * first.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dmem.p, members.data(), sizeof(int) * members.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && weights) e = hipMemcpyAsync(dw.p, weights, sizeof(double) * (size_t)t, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(plsa::k_rep_accumulate, dim3((unsigned)nb, (unsigned)n_clusters), dim3(256), 0, c->stream,
-                           T.as<float>(), (i64)m, dfirst.as<int>(), dmem.as<int>(), weights ? dw.as<double>() : nullptr,
-                           rep.as<double>(), bs.as<double>());
-        hipLaunchKernelGGL(plsa::k_rep_normalise, dim3((unsigned)nb, (unsigned)n_clusters), dim3(256), 0, c->stream,
-                           rep.as<double>(), (i64)m, bs.as<double>(), nb, dout.as<float>());
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, sizeof(float) * (size_t)n_clusters * m, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, "plsa_cluster_representatives: %s", hipGetErrorString(e));
-    return 0;
-}
-
 // Synthetic corpus in HBM (see plsa_synth.hpp).  The mean token count per document is calibrated
 // by a short secant iteration so that the number of DISTINCT (doc, word) pairs lands within 0.5 %
 // of nnz_target; the final matrix depends only on the arguments.
@@ -2326,3 +2004,5 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_smoothed.hpp"           // ... and the two loops and the objective
 #include "plsa_lda_kernels.hpp"        // variational Bayes LDA (plsa_hip_diag.h): exp-digamma tables, priors behind the passes, the bound ...
 #include "plsa_lda.hpp"                // ... and the two loops, the bound and the diagnostic read-back
+#include "plsa_combine_kernels.hpp"    // topic combination: all-pairs Hellinger and KL, cluster representatives ...
+#include "plsa_combine.hpp"            // ... and the six entry points, with the coherence counts and the embedding (their kernel headers)

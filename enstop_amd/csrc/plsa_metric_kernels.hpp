@@ -14,10 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plsa_combine_plan.hpp"
+
 namespace plsa {
 
-constexpr int METRIC_MAX_WORDS = 32;   // bits of a mask
-constexpr int METRIC_BLOCK = 256;
+using plan::METRIC_BLOCK;
+using plan::METRIC_MAX_WORDS;
 
 // grid (pieces of a posting list, nw, sets of the chunk).  words [sets][nw]; mask [sets][n] zeroed by the caller;
 // positive [sets][nw] zeroed by the caller: stored entries of the word whose value is > 0.

@@ -1,7 +1,7 @@
 """The topic-combination kernels against float64 restatements of the reference, entry for entry.
 
 After the bootstrapped fits everything EnsembleTopics returns goes through three kernel families of
-csrc/plsa_kernels.hpp: k_hell_prepare / k_hell_gram / k_hell_finish (plsa_all_pairs_hellinger), k_kl_gram / k_sum_slices
+csrc/plsa_combine_kernels.hpp: k_hell_prepare / k_hell_gram / k_hell_finish (plsa_all_pairs_hellinger), k_kl_gram / k_sum_slices
 (plsa_all_pairs_kl) and k_rep_accumulate / k_rep_normalise (plsa_cluster_representatives).  Here each is compared ELEMENTWISE
 with a float64 restatement written below (float64 GEMMs; none of them calls enstop_amd.ensemble's host functions):
 
@@ -80,7 +80,7 @@ TINY32 = 2.0 ** -149    # spacing of the float32 subnormals
 C_HELL = 3.0
 C_KL = 6.0
 C_REP = 6.0
-FLUSH = 256             # csrc/plsa_kernels.hpp: `since_flush >= 256`
+FLUSH = 256             # csrc/plsa_combine_kernels.hpp: `since_flush >= 256`
 TILE = 64               # HELL_TILE
 KSTEP = 32              # HELL_KSTEP
 MAX_TOPICS = 65536      # plsa_all_pairs_*: t > 65536 is refused
@@ -156,8 +156,9 @@ def representatives64(T, labels, weights=None):
 
 
 def host_slicing(t, m, cus, kind):
-    """csrc/plsa_hip.hip plsa_all_pairs_hellinger / plsa_all_pairs_kl restated: the number of vocabulary slices wanted
-    (`branch`), the words per slice (a multiple of the staging step) and the slices launched."""
+    """csrc/plsa_combine_plan.hpp vocab_slicing, as plsa_all_pairs_hellinger / plsa_all_pairs_kl (csrc/plsa_combine.hpp) call
+    it, restated: the number of vocabulary slices wanted (`branch`), the words per slice (a multiple of the staging step) and
+    the slices launched.  tests/test_combine_plan_host.py holds the header to this restatement."""
     nt = (t + TILE - 1) // TILE
     tiles = nt * (nt + 1) // 2 if kind == "hellinger" else nt * nt
     wanted = max(1, min(64, (4 * cus + tiles - 1) // tiles))
@@ -664,6 +665,23 @@ def test_degenerate_rows_and_labels(amd, worst):
     check_representatives("after the errors: representatives", eng.cluster_representatives(T, labels3),
                           representatives64(T, labels3))
     print("\ndegenerate rows: hellinger error / bound %.3g, kl %.3g, representatives (zero weights) %.3g" % (rh, rk, rr))
+
+
+@pytest.mark.gpu
+def test_more_clusters_than_grid_rows_are_refused_by_name(amd):
+    """A cluster is a row of the representatives' launch grid (gridDim.y, at most 65535): 65536 clusters are refused before
+    anything is allocated instead of failing at the launch; 65535 run.  The engine stays usable."""
+    from enstop_amd._lib import ptr
+    t, m = 8, 3
+    eng = amd.engine.get_engine()
+    T = np.random.RandomState(0).dirichlet(np.ones(m), size=t).astype(np.float32)
+    lab = np.arange(t, dtype=np.int32)
+    out = np.zeros((65536, m), np.float32)
+    assert eng._L.plsa_cluster_representatives(eng._h, ptr(T), t, m, lab, None, 65536, out) != 0
+    assert "n_clusters=65536" in eng._L.plsa_last_error(eng._h).decode()
+    assert eng._L.plsa_cluster_representatives(eng._h, ptr(T), t, m, lab, None, 65535, out) == 0
+    check_representatives("65535 clusters", out[:t], representatives64(T, lab))
+    assert np.isnan(out[t:65535]).all()                    # clusters without a member: NumPy's mean of an empty slice
 
 
 def _mem_available():
