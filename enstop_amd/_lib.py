@@ -193,6 +193,17 @@ ONLINE_SIGNATURES = {
     "plsa_online_fold": (C.c_int, [_online, _ctx, _vp, _i32, C.c_float, _i32]),
 }
 
+# enstop_amd/include/plsa_hip_lda_priors.h: LDA with a vector document-topic prior and learned priors (its own table as well)
+_f64p_c = C.POINTER(C.c_double)
+LDA_PRIOR_SIGNATURES = {
+    "plsa_lda_prior_fit": (C.c_int, [_ctx, _vp, _f64p_c, _i32, _i32, _i32, _i32, _i32, C.c_double, _i32, C.c_float, _i32,
+                                     C.POINTER(_i32), _vp, C.POINTER(_i32)]),
+    "plsa_lda_prior_refit": (C.c_int, [_ctx, _vp, _i32, _i32, C.c_double, _i32, C.c_float, _i32, C.POINTER(_i32), _vp,
+                                       C.POINTER(_i32)]),
+    "plsa_lda_prior_bound": (C.c_int, [_ctx, _vp, C.c_double, _i32, _f64p_c]),
+    "plsa_lda_prior_stats": (C.c_int, [_ctx, _vp, _vp]),
+}
+
 _lib = None
 HW_QUEUES ={"set_by": None, "hip_mapped_before_load": None}
 
@@ -244,7 +255,7 @@ def load():
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
             list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + \
-            list(TEMPERED_SIGNATURES.items()) + list(ONLINE_SIGNATURES.items()):
+            list(TEMPERED_SIGNATURES.items()) + list(ONLINE_SIGNATURES.items()) + list(LDA_PRIOR_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -8,7 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "plsa_hip.hip")
 # everything the one translation unit is made of: a new file is a dependency without being listed
 DEPS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.hip")) + glob.glob(os.path.join(HERE, "csrc", "*.hpp"))
-              + glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h")))
+              + glob.glob(os.path.join(os.path.dirname(HERE), "include", "*.h"))
+              + glob.glob(os.path.join(HERE, "include", "*.h")))
 OUT = os.path.join(HERE, "libplsa_hip.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))

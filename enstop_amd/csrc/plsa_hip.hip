@@ -38,6 +38,7 @@
 #include "../../include/plsa_hip_score.h"
 #include "../../include/plsa_hip_tempered.h"
 #include "../../include/plsa_hip_online.h"
+#include "../include/plsa_hip_lda_priors.h"
 #include "mt_jump.hpp"
 #include "plsa_init_kernels.hpp"
 #include "plsa_init_plan.hpp"
@@ -293,6 +294,10 @@ struct plsa_ctx {
     // norm_pdz [n] of the document pass in flight, the slab partials [2][256] of k_lda_bound, its two sums and the page-locked
     // slot they are copied to.  Kept between calls, freed by plsa_release_scratch
     struct Lda { DevBuf A, B, sums, norm_pdz, partials, out; Pinned<double> h_out; bool a_valid = false, b_valid = false; } lda;
+    // LDA's vector and learned priors (plsa_lda_priors.hpp): the prior vector as float64 [kp] and float32 [kp], the slab partials
+    // [min(4096, rows)][kp] of k_lda_logmean, its sums [2][kp] and the page-locked slot [4 kp] the sums arrive in and the vector
+    // leaves from.  Kept between calls, freed by plsa_release_scratch
+    struct LdaPrior { DevBuf alpha, partials, t; Pinned<double> h; int h_kp = 0; } lda_prior;
     DevBuf t_end;                    // end stamps of the column pass' timed tuning launches (ensure_balance)
     bool pipeline = true;            // PLSA_PIPELINE=0: fork/join form of the small-corpus iteration (A/B)
     bool graph = false;              // PLSA_GRAPH=1: hipGraph replay of the iterations between two likelihood tests
@@ -1772,11 +1777,14 @@ int plsa_release_scratch(plsa_ctx *c) {
                       &c->score.indptr, &c->score.col, &c->score.val, &c->score.flag, &c->score.out,
                       &c->tempered.U, &c->tempered.Vt, &c->tempered.snapU, &c->tempered.snapVt,
                       &c->smoothed.norm_pdz, &c->smoothed.partials, &c->smoothed.out,
-                      &c->lda.A, &c->lda.B, &c->lda.sums, &c->lda.norm_pdz, &c->lda.partials, &c->lda.out})
+                      &c->lda.A, &c->lda.B, &c->lda.sums, &c->lda.norm_pdz, &c->lda.partials, &c->lda.out,
+                      &c->lda_prior.alpha, &c->lda_prior.partials, &c->lda_prior.t})
         b->release();
     c->tempered.have_snap = false;
     c->smoothed.h_out.reset();           // (the stream is idle: nothing is on its way there)
     c->lda.h_out.reset();
+    c->lda_prior.h.reset();
+    c->lda_prior.h_kp = 0;
     c->lda.a_valid = c->lda.b_valid = false;
     // The page-locked landing buffer of plsa_comm_allgather_stack (c->comm_host) is NOT freed here: the caller may still
     // hold the pointer that call returned (a NumPy view in enstop_amd: gather_stack(view=True)); it lives until the next
@@ -2004,5 +2012,8 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_smoothed.hpp"           // ... and the two loops and the objective
 #include "plsa_lda_kernels.hpp"        // variational Bayes LDA (plsa_hip_diag.h): exp-digamma tables, priors behind the passes, the bound ...
 #include "plsa_lda.hpp"                // ... and the two loops, the bound and the diagnostic read-back
+#include "plsa_lda_prior_math.hpp"     // LDA's vector and learned priors (plsa_hip_lda_priors.h): trigamma and the two Newton maximisers ...
+#include "plsa_lda_prior_kernels.hpp"  // ... the sums a prior update needs, the vector forms of two kernels ...
+#include "plsa_lda_priors.hpp"         // ... and the loop with its prior updates, the refit, the bound and the sums
 #include "plsa_combine_kernels.hpp"    // topic combination: all-pairs Hellinger and KL, cluster representatives ...
 #include "plsa_combine.hpp"            // ... and the six entry points, with the coherence counts and the embedding (their kernel headers)

@@ -487,6 +487,52 @@ class Engine:
         self._ok(self._L.plsa_lda_tables(self._h, ptr(A), ptr(B)))
         return A, B
 
+    # -- LDA with a vector document-topic prior and learned priors (enstop_amd/include/plsa_hip_lda_priors.h) -----------------
+    def _prior_vector(self, doc_topic_prior):
+        alpha = np.ascontiguousarray(doc_topic_prior, np.float64).copy()
+        if alpha.shape != (self.k,):
+            raise ValueError("doc_topic_prior has shape %s, expected (%d,)" % (alpha.shape, self.k))
+        return alpha
+
+    def lda_prior_fit(self, doc_topic_prior, topic_word_prior, learn=3, prior_start=20, prior_every=1, n_iter=100,
+                      n_iter_per_test=10, tolerance=0.001, doc_iter=1, e_step_thresh=1e-32, flags=None, trace=False):
+        """lda_fit with doc_topic_prior a vector [k] and with priors that are re-estimated behind the iterations prior_start,
+        prior_start + prior_every, ... (counted from 1) by maximising the bound over them: learn bit 0 alpha, bit 1 eta, 0
+        neither.  Returns (iterations, trace, alpha [k], eta): the priors in force at the end.  A due test of the bound cannot
+        stop the loop before the first update.  lda_fit's refusals, and prior_start < 1, prior_every < 1."""
+        alpha = self._prior_vector(doc_topic_prior)
+        eta = C.c_double(float(topic_word_prior))
+
+        def fn(*rest):
+            return self._L.plsa_lda_prior_fit(self._h, ptr(alpha), C.byref(eta), int(learn), int(prior_start), int(prior_every),
+                                              *rest)
+        iters, bound = self._lda_drive(fn, n_iter, n_iter_per_test, tolerance, doc_iter, e_step_thresh, flags, trace)
+        return iters, bound, alpha, eta.value
+
+    def lda_prior_refit(self, doc_topic_prior, n_iter=50, n_iter_per_test=10, tolerance=0.005, doc_iter=1, e_step_thresh=1e-32,
+                        flags=None, trace=False):
+        """lda_refit under a vector prior [k]: only gamma moves, nothing is learned."""
+        alpha = self._prior_vector(doc_topic_prior)
+
+        def fn(*rest):
+            return self._L.plsa_lda_prior_refit(self._h, ptr(alpha), *rest)
+        return self._lda_drive(fn, n_iter, n_iter_per_test, tolerance, doc_iter, e_step_thresh, flags, trace)
+
+    def lda_prior_bound(self, doc_topic_prior, topic_word_prior=None):
+        """lda_bound under a vector prior [k]."""
+        alpha = self._prior_vector(doc_topic_prior)
+        out = C.c_double(0.0)
+        eta = 1.0 if topic_word_prior is None else float(topic_word_prior)
+        self._ok(self._L.plsa_lda_prior_bound(self._h, ptr(alpha), eta, 0 if topic_word_prior is None else 1, C.byref(out)))
+        return out.value
+
+    def lda_prior_stats(self):
+        """(t_doc [k], t_topic [k]) float64: sum_d (psi(gamma_dz) - psi(S_d)) and sum_w (psi(lambda_zw) - psi(S_z)) of the state
+        in force, the sums a prior update maximises over (diagnostics / tests)."""
+        t_doc, t_topic = np.zeros(self.k, np.float64), np.zeros(self.k, np.float64)
+        self._ok(self._L.plsa_lda_prior_stats(self._h, ptr(t_doc), ptr(t_topic)))
+        return t_doc, t_topic
+
     # -- doc-sharded fit building blocks ---------------------------------------------------------------
     def em_accumulate(self, sample_weight=None, e_step_thresh=1e-32, want_ll=False, materialised=False):
         """materialised: the reference's kernel sequence over this context's rows (E-step into P(z|w,d), M-step from it)
