@@ -1,6 +1,6 @@
 """ctypes binding of libplsa_hip.so (the C ABI of include/plsa_hip.h, plsa_hip_diag.h, plsa_hip_members.h,
 plsa_hip_metrics.h, plsa_hip_blocked.h, plsa_hip_embed.h, plsa_hip_nmf.h, plsa_hip_score.h, plsa_hip_tempered.h and
-plsa_hip_online.h).
+plsa_hip_online.h; enstop_amd/include/plsa_hip_lda_priors.h and plsa_hip_lda_online.h).
 
 There is no CPU fallback: if the HIP library is missing or no gfx950 device is visible, every entry
 point raises.  The library is built in-tree by ``python -m enstop_amd.build`` (or
@@ -204,6 +204,19 @@ LDA_PRIOR_SIGNATURES = {
     "plsa_lda_prior_stats": (C.c_int, [_ctx, _vp, _vp]),
 }
 
+# enstop_amd/include/plsa_hip_lda_online.h: online variational Bayes LDA on a state that outlives its block contexts (its own
+# table as well)
+_lda_online = C.c_void_p
+LDA_ONLINE_SIGNATURES = {
+    "plsa_lda_online_create": (C.c_int, [_ctx, _i64, _i32, C.POINTER(_lda_online)]),
+    "plsa_lda_online_destroy": (None, [_lda_online]),
+    "plsa_lda_online_set_lambda": (C.c_int, [_lda_online, _f32p]),
+    "plsa_lda_online_get_lambda": (C.c_int, [_lda_online, _vp, C.POINTER(_i64)]),
+    "plsa_lda_online_step": (C.c_int, [_lda_online, _ctx, C.c_double, C.c_double, _i32, C.c_float, C.c_double, C.c_double, _i32,
+                                       C.POINTER(C.c_double)]),
+    "plsa_lda_online_fold": (C.c_int, [_lda_online, _ctx, C.c_double, _i32, C.c_float, _i32]),
+}
+
 _lib = None
 HW_QUEUES ={"set_by": None, "hip_mapped_before_load": None}
 
@@ -255,7 +268,8 @@ def load():
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in list(SIGNATURES.items()) + list(MEMBER_SIGNATURES.items()) + list(METRIC_SIGNATURES.items()) + \
             list(BLOCKED_SIGNATURES.items()) + list(EMBED_SIGNATURES.items()) + list(NMF_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + \
-            list(TEMPERED_SIGNATURES.items()) + list(ONLINE_SIGNATURES.items()) + list(LDA_PRIOR_SIGNATURES.items()):
+            list(TEMPERED_SIGNATURES.items()) + list(ONLINE_SIGNATURES.items()) + list(LDA_PRIOR_SIGNATURES.items()) + \
+            list(LDA_ONLINE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

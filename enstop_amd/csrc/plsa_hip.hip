@@ -39,6 +39,7 @@
 #include "../../include/plsa_hip_tempered.h"
 #include "../../include/plsa_hip_online.h"
 #include "../include/plsa_hip_lda_priors.h"
+#include "../include/plsa_hip_lda_online.h"
 #include "mt_jump.hpp"
 #include "plsa_init_kernels.hpp"
 #include "plsa_init_plan.hpp"
@@ -2015,5 +2016,7 @@ int plsa_generate_synthetic_topics(plsa_ctx *c, int64_t n, int64_t m, int64_t nn
 #include "plsa_lda_prior_math.hpp"     // LDA's vector and learned priors (plsa_hip_lda_priors.h): trigamma and the two Newton maximisers ...
 #include "plsa_lda_prior_kernels.hpp"  // ... the sums a prior update needs, the vector forms of two kernels ...
 #include "plsa_lda_priors.hpp"         // ... and the loop with its prior updates, the refit, the bound and the sums
+#include "plsa_lda_online_kernels.hpp" // online LDA (plsa_hip_lda_online.h): the blend of the counts into lambda with its slab sums ...
+#include "plsa_lda_online.hpp"         // ... and the state, the step and the fold
 #include "plsa_combine_kernels.hpp"    // topic combination: all-pairs Hellinger and KL, cluster representatives ...
 #include "plsa_combine.hpp"            // ... and the six entry points, with the coherence counts and the embedding (their kernel headers)
