@@ -8,6 +8,10 @@
 // tables standing in for the factors (StandIn) -- run_row_pass handing norm_pdz back, run_col_pass(parts 3) leaving the raw
 // counts in Vacc -- and adds the priors behind the passes (k_lda_rows, k_lda_topics).  Both updates come from the same
 // responsibilities, so the bound (run_lda_bound) never decreases.  One stream, no look-ahead buffers, no hipGraph.
+//
+// Three pieces are here once for every form of LDA -- the vector and learned priors of plsa_lda_priors.hpp and the online step
+// and fold of plsa_lda_online.hpp enter them with their own parameters: the topic-side table chain (run_lda_topic_tables), the
+// round (LdaRounds) and the bound in an enqueue half and a finish half (lda_bound_send, lda_bound_finish).
 #pragma once
 
 namespace {
@@ -53,41 +57,55 @@ int run_lda_table_u(plsa_ctx *c, bool scaled = true) {
     return 0;
 }
 
-// B <- exp(psi(lambda) - psi(S_z) - shift_w) from Vt[cv]: S_z from float64 slab sums (k_lda_topic_partial) added in slab order,
-// shift_w the logarithm of the largest entry of word w's row
+// one topic side: lambda [m, kp], the table B formed from it, the float64 slab partials of lambda's column sums, S_z and
+// psi(S_z) [kp], the shift per word [m].  A context's own (lda_topic_side) or an online state's (plsa_lda_online.hpp)
+struct LdaTopicSide {
+    float4 *lam, *B;
+    double *slabs, *S, *psi, *shift;
+    i64 m;
+    int k, kp;
+};
+
+// B <- exp(psi(lambda) - psi(S_z) - shift_w) on c's stream: S_z from the float64 slab sums added in slab order (sweep:
+// k_lda_topic_partial forms them; otherwise the caller's kernel has left them), shift_w the logarithm of the largest entry of
+// word w's row (scaled; otherwise no shift).  The one place the topic-side chain is launched from
+int run_lda_topic_tables(plsa_ctx *c, const LdaTopicSide &t, bool sweep, bool scaled) {
+    const int kq = t.kp / 4, lanes = plsa::plan::lda_row_lanes(kq);
+    const i64 n4 = t.m * kq;
+    const int nb = plsa::plan::lda_bound_grid(t.m);
+    if (sweep) {
+        Scope s(c, "k_lda_topic_partial");
+        hipLaunchKernelGGL(plsa::k_lda_topic_partial, dim3(nb), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                           reinterpret_cast<const float *>(t.lam), (long long)t.m, t.kp, t.slabs);
+    }
+    {
+        Scope s(c, "k_lda_topic_sums");
+        hipLaunchKernelGGL(plsa::k_lda_topic_sums, dim3(plsa::plan::lda_topic_grid(t.kp)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                           t.slabs, nb, t.kp, t.k, t.S, t.psi);
+    }
+    if (scaled) {
+        Scope s(c, "k_lda_wordmax");
+        hipLaunchKernelGGL(plsa::k_lda_wordmax, dim3(plsa::plan::lda_rowsum_grid(t.m, kq, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0,
+                           c->ls, t.lam, (long long)t.m, kq, t.k, lanes, t.S, t.psi, t.shift);
+    }
+    {
+        Scope s(c, "k_lda_tables");
+        hipLaunchKernelGGL(plsa::k_lda_tables<false>, dim3(plsa::plan::lda_grid(n4, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
+                           t.lam, t.B, (long long)n4, kq, t.k, t.S, t.psi, scaled ? t.shift : nullptr);
+    }
+    return launch_check(c, "k_lda_tables");
+}
+
+// the table B of Vt[cv] in the context's side table, with its sums left in the context
 int run_lda_table_v(plsa_ctx *c, bool scaled = true) {
     plsa_ctx::Lda &l = c->lda;
     if (l.b_valid && scaled) return 0;
     l.b_valid = false;
     CHK(ensure(c, l.B, sizeof(float) * (size_t)c->m * c->kp));
     CHK(lda_ensure_sums(c));
-    const int kq = c->kp / 4, lanes = plsa::plan::lda_row_lanes(kq);
-    const i64 n4 = c->m * kq;
-    const int nb = plsa::plan::lda_bound_grid(c->m);
-    CHK(ensure(c, c->colsum_partials, sizeof(double) * (size_t)nb * c->kp));
-    {
-        Scope s(c, "k_lda_topic_partial");
-        hipLaunchKernelGGL(plsa::k_lda_topic_partial, dim3(nb), dim3(plsa::plan::LDA_BLOCK), 0, c->ls, c->Vt[c->cv].as<float>(),
-                           (long long)c->m, c->kp, c->colsum_partials.as<double>());
-    }
-    {
-        Scope s(c, "k_lda_topic_sums");
-        hipLaunchKernelGGL(plsa::k_lda_topic_sums, dim3(plsa::plan::lda_topic_grid(c->kp)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
-                           c->colsum_partials.as<double>(), nb, c->kp, c->k, lda_sums(c, LDA_S_TOPIC), lda_sums(c, LDA_PSI_TOPIC));
-    }
-    if (scaled) {
-        Scope s(c, "k_lda_wordmax");
-        hipLaunchKernelGGL(plsa::k_lda_wordmax, dim3(plsa::plan::lda_rowsum_grid(c->m, kq, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0,
-                           c->ls, c->Vt[c->cv].as<float4>(), (long long)c->m, kq, c->k, lanes, lda_sums(c, LDA_S_TOPIC),
-                           lda_sums(c, LDA_PSI_TOPIC), lda_sums(c, LDA_SHIFT_WORD));
-    }
-    {
-        Scope s(c, "k_lda_tables");
-        hipLaunchKernelGGL(plsa::k_lda_tables<false>, dim3(plsa::plan::lda_grid(n4, c->grid_cap)), dim3(plsa::plan::LDA_BLOCK), 0, c->ls,
-                           c->Vt[c->cv].as<float4>(), l.B.as<float4>(), (long long)n4, kq, c->k, lda_sums(c, LDA_S_TOPIC),
-                           lda_sums(c, LDA_PSI_TOPIC), scaled ? lda_sums(c, LDA_SHIFT_WORD) : nullptr);
-    }
-    CHK(launch_check(c, "k_lda_tables"));
+    CHK(ensure(c, c->colsum_partials, sizeof(double) * (size_t)plsa::plan::lda_bound_grid(c->m) * c->kp));
+    CHK(run_lda_topic_tables(c, {c->Vt[c->cv].as<float4>(), l.B.as<float4>(), c->colsum_partials.as<double>(), lda_sums(c, LDA_S_TOPIC),
+                                 lda_sums(c, LDA_PSI_TOPIC), lda_sums(c, LDA_SHIFT_WORD), c->m, c->k, c->kp}, true, scaled));
     l.b_valid = scaled;
     return 0;
 }
@@ -149,31 +167,98 @@ int run_lda_shift_sum(plsa_ctx *c) {
 }
 
 // L = sum x_dw log sum_z A_dz B_zw + the Dirichlet part of gamma (+ the Dirichlet part of lambda: with_topics) of the state in
-// force.  The likelihood term is k_loglik on the scaled tables plus the shifts the scaling took out; the constants
-// lgamma(k alpha) - k lgamma(alpha) per document and lgamma(m eta) - m lgamma(eta) per topic are added here
-int run_lda_bound(plsa_ctx *c, double alpha, double eta, bool with_topics, double *out) {
+// force, in two halves.  The likelihood term is k_loglik on the scaled tables plus the shifts the scaling took out.
+//
+// The enqueue half: the sums, launched in one order for every caller, with no host wait.  `gamma_part` launches the Dirichlet
+// part of gamma into c->lda.out[0] (run_lda_dirichlet<true> under a scalar alpha, run_lda_dirichlet_v under a vector); `who`
+// names the entry point in the one refusal
+template <class GammaPart>
+int lda_bound_send(plsa_ctx *c, const char *who, GammaPart gamma_part, double eta, bool with_topics) {
     plsa_ctx::Lda &l = c->lda;
     // the sums land in a page-locked slot of the context: a copy still on its way writes to memory that outlives the call
-    if (!l.h_out && host_alloc(l.h_out, 3) != hipSuccess) return fail(c, "plsa_lda_bound: page-locked buffer allocation failed");
-    double *part = l.h_out.get();
+    if (!l.h_out && host_alloc(l.h_out, 3) != hipSuccess) return fail(c, "%s: page-locked buffer allocation failed", who);
     CHK(ensure(c, l.partials, sizeof(double) * (2 * plsa::plan::PRIOR_SLABS + plsa::plan::LDA_SHIFT_SLABS)));
     CHK(ensure(c, l.out, sizeof(double) * 3));
     CHK(run_lda_table_u(c));
     CHK(run_lda_table_v(c));
-    CHK(run_lda_dirichlet<true>(c, c->U[c->cu], c->n, alpha, 0));
+    CHK(gamma_part());
     if (with_topics) CHK(run_lda_dirichlet<false>(c, c->Vt[c->cv], c->m, eta, 1));
     CHK(run_lda_shift_sum(c));
-    HIPCHK(c, hipMemcpyAsync(part, l.out.as<double>(), sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(l.h_out.get(), l.out.as<double>(), sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+    StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
+    return run_loglik(c, nullptr, nullptr);                  // sent behind the other sums: its event covers them as well
+}
+
+// The finish half: the host waits for the likelihood's event (not for what was enqueued behind it) and adds, in this order, the
+// shifts, the gamma part with n times `doc_constant` -- lgamma(k alpha) - k lgamma(alpha), or lgamma(sum alpha) - sum
+// lgamma(alpha_z), computed by the caller -- and with_topics the lambda part with k (lgamma(m eta) - m lgamma(eta))
+int lda_bound_finish(plsa_ctx *c, double doc_constant, double eta, bool with_topics, double *out) {
     double ll = 0.0;
-    {
-        StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
-        CHK(run_loglik(c, nullptr, &ll));    // waits for c->stream: the other sums have arrived as well
-    }
+    CHK(wait_ll(c, &ll));
+    const double *part = c->lda.h_out.get();
     ll += part[2];
-    ll += part[0] + (double)c->n * (lgamma(c->k * alpha) - c->k * lgamma(alpha));
+    ll += part[0] + (double)c->n * doc_constant;
     if (with_topics) ll += part[1] + (double)c->k * (lgamma((double)c->m * eta) - (double)c->m * lgamma(eta));
     *out = ll;
     return 0;
+}
+
+auto lda_gamma_part(plsa_ctx *c, double alpha) {
+    return [c, alpha] { return run_lda_dirichlet<true>(c, c->U[c->cu], c->n, alpha, 0); };
+}
+double lda_doc_constant(plsa_ctx *c, double alpha) { return lgamma(c->k * alpha) - c->k * lgamma(alpha); }
+
+int run_lda_bound(plsa_ctx *c, double alpha, double eta, bool with_topics, double *out) {
+    CHK(lda_bound_send(c, "plsa_lda_bound", lda_gamma_part(c, alpha), eta, with_topics));
+    return lda_bound_finish(c, lda_doc_constant(c, alpha), eta, with_topics, out);
+}
+
+// what becomes of the column pass of a round: not run; run, the raw counts left in Vacc (the online step: the block's Vt is
+// neither written nor flipped); run, lambda <- eta + the counts into Vt[out_v], which becomes the table in force
+enum class LdaColumns { NONE, COUNTS, TOPICS };
+
+// The LDA round, for the batch fits, the fits with a vector prior, the online step and the online fold: tables -> document
+// pass (-> column pass) under StandIn -> rows -> flip.  `rows` launches gamma <- alpha + the document pass's counts
+// (run_lda_rows under a scalar alpha, run_lda_rows_v under a vector); `columns` is what the last round of an iteration does
+template <class Rows>
+struct LdaRounds {
+    plsa_ctx *c;
+    float thresh;
+    Rows rows;
+    LdaColumns columns;
+    double eta;
+    int round(bool with_columns) {
+        plsa_ctx::Lda &l = c->lda;
+        const bool topics = with_columns && columns == LdaColumns::TOPICS;
+        CHK(run_lda_table_u(c));
+        CHK(run_lda_table_v(c));
+        CHK(ensure(c, l.norm_pdz, sizeof(float) * (size_t)c->n));
+        {
+            StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
+            CHK(run_row_pass(c, false, false, nullptr, thresh, l.norm_pdz.as<float>(), nullptr));
+            if (with_columns) CHK(run_col_pass(c, false, nullptr, thresh, 3));
+        }
+        CHK(rows());
+        if (topics) CHK(run_lda_topics(c, eta));
+        c->cu ^= 1;
+        l.a_valid = false;
+        if (topics) { c->cv ^= 1; l.b_valid = false; }
+        return 0;
+    }
+    // doc_iter - 1 gamma-only rounds, then one with the caller's mode
+    int iteration(int doc_iter) {
+        for (int r = 1; r < doc_iter; ++r) CHK(round(false));
+        return round(columns != LdaColumns::NONE);
+    }
+};
+
+template <class Rows>
+LdaRounds<Rows> lda_rounds(plsa_ctx *c, float thresh, Rows rows, LdaColumns columns, double eta) {
+    return {c, thresh, rows, columns, eta};
+}
+
+auto lda_scalar_rows(plsa_ctx *c, double alpha) {
+    return [c, alpha] { return run_lda_rows(c, alpha); };
 }
 
 // the reference's loop (fit::run_materialised) over LDA iterations.  update_v = false: the refit -- gamma only, lambda is never
@@ -185,28 +270,8 @@ struct LdaBackend {
     int doc_iter;
     bool update_v;
     int loglik(double *f) { return run_lda_bound(c, alpha, eta, update_v, f); }
-    // gamma <- alpha + the document pass's counts under the tables in force; with_topics: lambda <- eta + the column pass's
-    // counts under the same tables
-    int round(bool with_topics) {
-        plsa_ctx::Lda &l = c->lda;
-        CHK(run_lda_table_u(c));
-        CHK(run_lda_table_v(c));
-        CHK(ensure(c, l.norm_pdz, sizeof(float) * (size_t)c->n));
-        {
-            StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
-            CHK(run_row_pass(c, false, false, nullptr, thresh, l.norm_pdz.as<float>(), nullptr));
-            if (with_topics) CHK(run_col_pass(c, false, nullptr, thresh, 3));
-        }
-        CHK(run_lda_rows(c, alpha));
-        if (with_topics) CHK(run_lda_topics(c, eta));
-        c->cu ^= 1;
-        l.a_valid = false;
-        if (with_topics) { c->cv ^= 1; l.b_valid = false; }
-        return 0;
-    }
     int iteration() {
-        for (int r = 1; r < doc_iter; ++r) CHK(round(false));
-        return round(update_v);
+        return lda_rounds(c, thresh, lda_scalar_rows(c, alpha), update_v ? LdaColumns::TOPICS : LdaColumns::NONE, eta).iteration(doc_iter);
     }
 };
 

@@ -1,7 +1,7 @@
 // plsa_lda_priors.hpp -- host side of LDA with a vector document-topic prior and learned priors: plsa_lda_prior_fit,
 // plsa_lda_prior_refit, plsa_lda_prior_bound and plsa_lda_prior_stats (enstop_amd/include/plsa_hip_lda_priors.h, DESIGN.md
 // section 20); part of plsa_hip.hip's translation unit (included at its end, behind plsa_lda.hpp: it uses its tables, its
-// topic side, its bound's sums, and the call frame of plsa_drivers.hpp).
+// topic side, its round, its bound, and the call frame of plsa_drivers.hpp).
 //
 // The prior vector lives on the device twice, float64 [kp] for the bound and float32 [kp] for k_lda_rows_v (0 at the pads),
 // sent from a page-locked slot that also receives the sums T_z of a prior update.  An update runs behind a round: the tables
@@ -69,31 +69,12 @@ int run_lda_dirichlet_v(plsa_ctx *c) {
 }
 
 // run_lda_bound with the vector prior on the device (lda_prior_send) and in alpha [k]: the document constant is
-// n (lgamma(sum alpha) - sum lgamma(alpha_z))
+// lgamma(sum alpha) - sum lgamma(alpha_z)
 int run_lda_bound_v(plsa_ctx *c, const double *alpha, double eta, bool with_topics, double *out) {
-    plsa_ctx::Lda &l = c->lda;
-    if (!l.h_out && host_alloc(l.h_out, 3) != hipSuccess) return fail(c, "plsa_lda_prior_bound: page-locked buffer allocation failed");
-    double *part = l.h_out.get();
-    CHK(ensure(c, l.partials, sizeof(double) * (2 * plsa::plan::PRIOR_SLABS + plsa::plan::LDA_SHIFT_SLABS)));
-    CHK(ensure(c, l.out, sizeof(double) * 3));
-    CHK(run_lda_table_u(c));
-    CHK(run_lda_table_v(c));
-    CHK(run_lda_dirichlet_v(c));
-    if (with_topics) CHK(run_lda_dirichlet<false>(c, c->Vt[c->cv], c->m, eta, 1));
-    CHK(run_lda_shift_sum(c));
-    HIPCHK(c, hipMemcpyAsync(part, l.out.as<double>(), sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
-    double ll = 0.0;
-    {
-        StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
-        CHK(run_loglik(c, nullptr, &ll));    // waits for c->stream: the other sums have arrived as well
-    }
+    CHK(lda_bound_send(c, "plsa_lda_prior_bound", [c] { return run_lda_dirichlet_v(c); }, eta, with_topics));
     double sum = 0.0, each = 0.0;
     for (int z = 0; z < c->k; ++z) { sum += alpha[z]; each += lgamma(alpha[z]); }
-    ll += part[2];
-    ll += part[0] + (double)c->n * (lgamma(sum) - each);
-    if (with_topics) ll += part[1] + (double)c->k * (lgamma((double)c->m * eta) - (double)c->m * lgamma(eta));
-    *out = ll;
-    return 0;
+    return lda_bound_finish(c, lgamma(sum) - each, eta, with_topics, out);
 }
 
 // slot T (0: gamma, BY_ROW; 1: lambda) of c->lda_prior.t [2][kp] <- the sums of psi(entry) - psi(S) per topic, from the sums of
@@ -134,7 +115,7 @@ int run_lda_prior_stats(plsa_ctx *c, bool docs, bool topics) {
     return 0;
 }
 
-// LdaBackend with the vector prior, and the prior update
+// LdaBackend with the vector prior -- its own: the alpha vector, the rows step, the prior update
 struct LdaPriorBackend {
     plsa_ctx *c;
     float thresh;
@@ -143,26 +124,9 @@ struct LdaPriorBackend {
     int doc_iter;
     bool update_v;
     int loglik(double *f) { return run_lda_bound_v(c, alpha.data(), eta, update_v, f); }
-    int round(bool with_topics) {
-        plsa_ctx::Lda &l = c->lda;
-        CHK(run_lda_table_u(c));
-        CHK(run_lda_table_v(c));
-        CHK(ensure(c, l.norm_pdz, sizeof(float) * (size_t)c->n));
-        {
-            StandIn u(c->U[c->cu], l.A), v(c->Vt[c->cv], l.B);
-            CHK(run_row_pass(c, false, false, nullptr, thresh, l.norm_pdz.as<float>(), nullptr));
-            if (with_topics) CHK(run_col_pass(c, false, nullptr, thresh, 3));
-        }
-        CHK(run_lda_rows_v(c));
-        if (with_topics) CHK(run_lda_topics(c, eta));
-        c->cu ^= 1;
-        l.a_valid = false;
-        if (with_topics) { c->cv ^= 1; l.b_valid = false; }
-        return 0;
-    }
     int iteration() {
-        for (int r = 1; r < doc_iter; ++r) CHK(round(false));
-        return round(update_v);
+        return lda_rounds(c, thresh, [this] { return run_lda_rows_v(c); }, update_v ? LdaColumns::TOPICS : LdaColumns::NONE, eta)
+            .iteration(doc_iter);
     }
     // alpha (learn bit 0) and eta (bit 1) <- the maximisers of the bound at the state in force
     int update_priors(int learn) {

@@ -13,8 +13,10 @@ the documents into blocks and updates lambda after every block, with a decaying 
     the corpus (lda_fit_online) or the promised `total_samples` (partial_fit).  At rho = 1 and scale = 1 a step is one
     iteration of lda_fit on the block, to the bit.
 
-  LdaOnlineState    the device-side state (lambda, its tables, t) behind the C ABI; steps and folds are driven through it
-  lda_fit_online    cuts X into blocks of whole documents, one context each, and drives online.OnlineSchedule
+  LdaOnlineState    the device-side state (lambda, its tables, t) behind the C ABI (online.DeviceState's frame); steps and folds
+                    are driven through it
+  lda_fit_online    cuts X into blocks of whole documents, one context each (online.cut_blocks), and drives
+                    online.OnlineSchedule through online.drive_blocks
   OnlineLDA         the estimator: fit / fit_transform through lda_fit_online, and partial_fit for documents in pieces
 
 alpha and eta are fixed scalars here; vectors, "asymmetric" and "auto" (lda.py) have no online form yet, nor have sample weights.
@@ -32,61 +34,29 @@ from sklearn.utils import check_random_state
 
 from . import _lib
 from ._driver import resolve_flags
-from ._lib import PLSA_FUSED, PLSA_REFERENCE_LL, PLSA_REFERENCE_SUMS, ptr
+from ._lib import ptr
 from .engine import Engine, get_engine
 from .lda import LDA, _counts, _resolve_count, lda_init, resolve_prior
-from .online import _ABI_FLAGS, MAX_BATCHES, OnlineSchedule, block_tokens
+from .online import (_ABI_FLAGS, MAX_BATCHES, DeviceState, OnlineSchedule, PartialFitMixin, block_tokens, cut_blocks, drive_blocks,
+                     plain_fused_flags)
 from .plsa import _locked
-from .sharded import row_ranges_by_nnz
 
 
-class LdaOnlineState:
+class LdaOnlineState(DeviceState):
     """lambda, the tables formed from it and the step counter on the device of `home` (an Engine, which must outlive the
     state: the host copies of lambda go through its stream).  One ABI call per method."""
-
-    def __init__(self, home, m, k):
-        self._L = _lib.load()
-        self.home = home
-        self.m, self.k = int(m), int(k)
-        self._h = C.c_void_p()
-        home._ok(self._L.plsa_lda_online_create(home._h, self.m, self.k, C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            if self.home._h.value:              # (a state dies with its home engine)
-                self._L.plsa_lda_online_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    _prefix = "plsa_lda_online"
+    _counter = "plsa_lda_online_get_lambda"
 
     def set_lambda(self, lam):
         """lambda := lam [k, m], the tables formed from it, t := 0"""
-        lam = np.ascontiguousarray(lam, dtype=np.float32)
-        if lam.shape != (self.k, self.m):
-            raise ValueError("the table has shape %s, expected %s" % (lam.shape, (self.k, self.m)))
-        self.home._ok(self._L.plsa_lda_online_set_lambda(self._h, lam))
+        self.home._ok(self._L.plsa_lda_online_set_lambda(self._h, self._table(lam)))
         return self
 
     def get_lambda(self):
         lam = np.empty((self.k, self.m), np.float32)
         self.home._ok(self._L.plsa_lda_online_get_lambda(self._h, ptr(lam), None))
         return lam
-
-    @property
-    def steps(self):
-        t = C.c_int64(0)
-        self.home._ok(self._L.plsa_lda_online_get_lambda(self._h, None, C.byref(t)))
-        return t.value
 
     def step(self, eng, doc_topic_prior, topic_word_prior, rho, scale, doc_iter=3, e_step_thresh=1e-32, want_bound=False,
              flags=None):
@@ -127,61 +97,10 @@ def _resolve_online(k, doc_topic_prior, topic_word_prior, n_batches, n_epochs, d
     return k, alpha, eta, n_batches, _resolve_count("n_epochs", n_epochs, 0), _resolve_count("doc_iter", doc_iter, 1)
 
 
-def _plain_fused_flags():
-    flags = resolve_flags(None)
-    if not flags & PLSA_FUSED or flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL):
-        raise ValueError("online LDA runs the fused schedule in the default arithmetic only "
-                         "(ENSTOP_AMD_MATERIALISE / ENSTOP_AMD_ARITHMETIC are set)")
-    return flags
-
-
 @_locked
-def _fit_online(X, gamma0, lam0, alpha, eta, schedule, perm, ranges, doc_iter, e_step_thresh, device, return_info, callback, flags):
-    n, m = X.shape
-    k = gamma0.shape[1]
-    n_blocks = len(ranges)
-    want_bound = bool(return_info) or schedule.tolerance > 0.0
-    home = get_engine(device)
-    engines, state = [], None
-    try:
-        scales, tokens = [], []
-        for a, b in ranges:
-            eng = Engine(home.device)
-            engines.append(eng)
-            eng.upload_csr(X[a:b])
-            eng.set_factors(gamma0[a:b], lam0)
-            tokens.append(block_tokens(X[a:b]))
-            scales.append(float(n) / float(b - a))
-        state = LdaOnlineState(home, m, k).set_lambda(lam0)
-        _, acc_floats = engines[0].accumulator_device()
-        info = dict(n_epochs=0, n_steps=0, rho=schedule.rhos, bounds=schedule.log_likelihoods, block_ranges=ranges,
-                    permutation=perm, tokens=tokens, bytes_per_block_context=3 * 4 * int(acc_floats))
-        epoch_bound = 0.0
-        while True:
-            step = schedule.next_step()
-            if step is None:
-                break
-            _, block, rho_t = step
-            bound = state.step(engines[block], alpha, eta, rho_t, scales[block], doc_iter, e_step_thresh, want_bound, flags)
-            epoch_bound += bound if want_bound else float("nan")
-            if block == n_blocks - 1:
-                schedule.end_epoch(epoch_bound)
-                epoch_bound = 0.0
-                info.update(n_epochs=schedule.n_epochs_done, n_steps=schedule.n_steps)
-                if callback is not None:
-                    callback(info, state)
-        gamma = np.zeros((n, k), np.float32)
-        for eng in engines:
-            state.fold(eng, alpha, max(doc_iter, 1), e_step_thresh, flags)
-        for eng, (a, b) in zip(engines, ranges):
-            gamma[a:b] = eng.get_factors(want_v=False)[0]
-        lam = state.get_lambda()
-    finally:
-        if state is not None:
-            state.close()
-        for eng in engines:
-            eng.close()
-    return gamma, lam, info
+def _drive_locked(device, pieces):
+    """drive_blocks under the lock of the device's engine, with the home engine handed to the pieces"""
+    return drive_blocks(**pieces(get_engine(device)))
 
 
 def lda_fit_online(X, k, doc_topic_prior=None, topic_word_prior=None, init="random", n_batches=64, n_epochs=5, doc_iter=3,
@@ -209,7 +128,7 @@ def lda_fit_online(X, k, doc_topic_prior=None, topic_word_prior=None, init="rand
     touched.  Default arithmetic, fused schedule only; no sample weights."""
     k, alpha, eta, n_batches, n_epochs, doc_iter = _resolve_online(k, doc_topic_prior, topic_word_prior, n_batches, n_epochs,
                                                                    doc_iter, tolerance)
-    flags = _plain_fused_flags()
+    flags = plain_fused_flags("online LDA")
     X = _counts(X)
     n, m = X.shape
     n_blocks = min(n_batches, n)
@@ -218,24 +137,27 @@ def lda_fit_online(X, k, doc_topic_prior=None, topic_word_prior=None, init="rand
     schedule = OnlineSchedule(n_blocks, n_epochs, kappa, tau0, rho, tolerance)
     rng = check_random_state(random_state)
     gamma0, lam0 = lda_init(X, k, init, rng)
-    perm = rng.permutation(n) if shuffle_documents else None
-    if perm is not None:
-        X, gamma0 = X[perm], gamma0[perm]
-    ranges = row_ranges_by_nnz(X.indptr, n_blocks)
-    if any(b <= a for a, b in ranges):
-        raise ValueError("lda_fit_online: %d documents cannot be split over %d blocks" % (n, n_blocks))
-    gamma, lam, info = _fit_online(X, gamma0, lam0, alpha, eta, schedule, perm, ranges, doc_iter, e_step_thresh, device,
-                                   return_info, callback, flags)
-    if perm is not None:
-        out = np.empty_like(gamma)
-        out[perm] = gamma
-        gamma = out
-    if return_info:
-        return gamma, lam, dict(info, rho=list(schedule.rhos), bounds=list(schedule.log_likelihoods))
-    return gamma, lam
+    X, (gamma0,), perm, ranges, undo = cut_blocks("lda_fit_online", X, n_blocks, rng, shuffle_documents, gamma0)
+
+    def setup(eng, i, a, b):
+        eng.upload_csr(X[a:b])
+        eng.set_factors(gamma0[a:b], lam0)
+        return block_tokens(X[a:b]), float(n) / float(b - a)
+
+    def pieces(home):
+        return dict(
+            n=n, k=k, ranges=ranges, perm=perm, schedule=schedule, want=bool(return_info) or schedule.tolerance > 0.0,
+            series="bounds", new_engine=lambda: Engine(home.device), setup=setup,
+            make_state=lambda: LdaOnlineState(home, m, k).set_lambda(lam0),
+            step=lambda state, eng, rho_t, scale, want: state.step(eng, alpha, eta, rho_t, scale, doc_iter, e_step_thresh, want, flags),
+            fold=lambda state, eng: state.fold(eng, alpha, max(doc_iter, 1), e_step_thresh, flags),
+            rows=lambda eng: eng.get_factors(want_v=False)[0], topics=lambda state: state.get_lambda(), callback=callback)
+
+    gamma, lam, info = _drive_locked(device, pieces)
+    return (undo(gamma), lam, info) if return_info else (undo(gamma), lam)
 
 
-class OnlineLDA(LDA):
+class OnlineLDA(PartialFitMixin, LDA):
     """LDA fitted by online variational Bayes (lda_fit_online; module docstring): `components_`, `topic_word_`, `embedding_`,
     `training_data_`, `doc_topic_prior_`, `topic_word_prior_` as LDA's, `n_iter_` = epochs run, `n_steps_` = steps taken,
     `online_info_` = lda_fit_online's info, `bound_trace_` = L_e per epoch (progressive, without the topic part) and `bound_`
@@ -297,24 +219,7 @@ class OnlineLDA(LDA):
         self.bound_ = float(self.bound_trace_[-1]) if len(self.bound_trace_) else float("nan")
         return self.embedding_
 
-    # -- documents in pieces -------------------------------------------------------------------------------------------
-    def _end_partial(self):
-        p = self.__dict__.pop("_partial", None)
-        if p is not None:
-            p["state"].close()
-            p["engine"].close()
-
-    def __getstate__(self):                      # device handles do not travel: a copy starts partial_fit afresh
-        state = dict(self.__dict__)
-        state.pop("_partial", None)
-        return state
-
-    def __del__(self):
-        try:
-            self._end_partial()
-        except Exception:
-            pass
-
+    # -- documents in pieces (online.PartialFitMixin) -------------------------------------------------------------------
     def partial_fit(self, X, y=None):
         (alpha, _), (eta, _) = self._priors()
         k = int(self.n_components)
@@ -322,7 +227,7 @@ class OnlineLDA(LDA):
         total = self.total_samples
         if isinstance(total, bool) or not isinstance(total, numbers.Real) or not np.isfinite(total) or not total > 0:
             raise ValueError("total_samples=%r: expected a finite number > 0" % (total,))
-        flags = _plain_fused_flags()
+        flags = plain_fused_flags("online LDA")
         X = _counts(X)
         n, m = X.shape
         if n < 1:

@@ -11,7 +11,9 @@ documents into blocks and updates P(w|z) after every block from a running suffic
     rho_t = (tau0 + t)^(-kappa) for t = 0, 1, ... (a fixed `rho` overrides it);  scale_b = 1 / (weighted tokens of block b),
     so the statistic is per token and no corpus size has to be promised in advance;  S_0 = V0 / k.
 
-  OnlineState       the device-side state (V, S, t) behind the C ABI; steps and folds are driven through it
+  DeviceState       the frame of a device-side state behind the C ABI (shared with lda_online.LdaOnlineState)
+  OnlineState       the device-side state (V, S, t); steps and folds are driven through it
+  cut_blocks, drive_blocks   the permutation and block cutting, and the block loop, of both online fits: no engine in them
   OnlineSchedule    a state machine without an engine in it: hands out (epoch, block, rho) and takes each epoch's likelihood
   plsa_fit_online   cuts X into blocks of whole documents, one context each, and drives the schedule
   OnlinePLSA        the estimator: fit / fit_transform through plsa_fit_online, and partial_fit for documents in pieces
@@ -38,21 +40,24 @@ MAX_BATCHES = 256          # every block context carries three [m, kp] tables of
 _ABI_FLAGS = PLSA_FUSED | PLSA_SHARDED | PLSA_GRAPH | PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL      # the bits a step looks at
 
 
-class OnlineState:
-    """The topics V, the statistic S and the step counter on the device of `home` (an Engine, which must outlive the state:
-    the host copies of V and S go through its stream).  One ABI call per method."""
+class DeviceState:
+    """The frame of a device-side online state behind the C ABI, on the device of `home` (an Engine, which must outlive the
+    state: the host copies of its [k, m] tables go through its stream).  A subclass names the prefix of its entry points
+    (`_prefix`_create / _destroy) and the entry point that reports the step counter, called as (state, NULL, &t)."""
+    _prefix = None
+    _counter = None
 
     def __init__(self, home, m, k):
         self._L = _lib.load()
         self.home = home
         self.m, self.k = int(m), int(k)
         self._h = C.c_void_p()
-        home._ok(self._L.plsa_online_create(home._h, self.m, self.k, C.byref(self._h)))
+        home._ok(getattr(self._L, self._prefix + "_create")(home._h, self.m, self.k, C.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             if self.home._h.value:              # (a state dies with its home engine)
-                self._L.plsa_online_destroy(self._h)
+                getattr(self._L, self._prefix + "_destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -73,6 +78,19 @@ class OnlineState:
             raise ValueError("the table has shape %s, expected %s" % (a.shape, (self.k, self.m)))
         return a
 
+    @property
+    def steps(self):
+        t = C.c_int64(0)
+        self.home._ok(getattr(self._L, self._counter)(self._h, None, C.byref(t)))
+        return t.value
+
+
+class OnlineState(DeviceState):
+    """The topics V, the statistic S and the step counter on the device of `home` (an Engine, which must outlive the state:
+    the host copies of V and S go through its stream).  One ABI call per method."""
+    _prefix = "plsa_online"
+    _counter = "plsa_online_statistic_get"
+
     def set_topics(self, topics):
         """V := topics [k, m], S := topics / k, t := 0"""
         self.home._ok(self._L.plsa_online_set_topics(self._h, self._table(topics)))
@@ -91,12 +109,6 @@ class OnlineState:
     def statistic_set(self, S):
         self.home._ok(self._L.plsa_online_statistic_set(self._h, self._table(S)))
         return self
-
-    @property
-    def steps(self):
-        t = C.c_int64(0)
-        self.home._ok(self._L.plsa_online_statistic_get(self._h, None, C.byref(t)))
-        return t.value
 
     def step(self, eng, rho, scale, inner_iter=0, sample_weight=None, e_step_thresh=1e-32, want_ll=False, flags=None):
         """One step on the block resident on `eng` (module docstring); -> the block's log-likelihood under the factors the
@@ -195,6 +207,92 @@ def _csr(X):
     return X.tocsr() if issparse(X) else csr_matrix(X)
 
 
+def plain_fused_flags(form):
+    """The resolved flags of a fit of `form` ("online EM", "online LDA"), which runs the plain fused schedule only"""
+    flags = resolve_flags(None)
+    if not flags & PLSA_FUSED or flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL):
+        raise ValueError("%s runs the fused schedule in the default arithmetic only "
+                         "(ENSTOP_AMD_MATERIALISE / ENSTOP_AMD_ARITHMETIC are set)" % form)
+    return flags
+
+
+def cut_blocks(who, X, n_blocks, rng, shuffle, *per_document):
+    """ONE permutation of the documents drawn from `rng` (shuffle), applied to X and to every per-document array (None stays
+    None), and the permuted documents cut into n_blocks ranges of whole documents with about equal non-zeros; ->
+    (X, per_document, perm, ranges, undo), undo(rows) putting rows of the permuted documents back into the caller's order"""
+    n = X.shape[0]
+    perm = rng.permutation(n) if shuffle else None
+    if perm is not None:
+        X = X[perm]
+        per_document = [None if a is None else a[perm] for a in per_document]
+    ranges = row_ranges_by_nnz(X.indptr, n_blocks)
+    if any(b <= a for a, b in ranges):
+        raise ValueError("%s: %d documents cannot be split over %d blocks" % (who, n, n_blocks))
+
+    def undo(rows):
+        if perm is None:
+            return rows
+        out = np.empty_like(rows)
+        out[perm] = rows
+        return out
+    return X, list(per_document), perm, ranges, undo
+
+
+def drive_blocks(n, k, ranges, perm, schedule, want, series, new_engine, setup, make_state, step, fold, rows, topics,
+                 callback=None):
+    """The block loop of both online fits.  It imports no engine: everything that touches a device comes in as a callable.
+
+        new_engine()             -> the context of one block (one per range, opened in block order)
+        setup(eng, i, a, b)      -> (tokens, scale) of block i, documents a .. b, once it is resident on eng
+        make_state()             -> the device state, made after every block is set up
+        step(state, eng, rho, scale, want) -> the block's term of the epoch sum (read only when `want`)
+        fold(state, eng), rows(eng), topics(state)   the final pass over a block, its rows [b - a, k], the state's [k, m] table
+
+    Steps follow `schedule`; an epoch's sum (NaN when nothing is read) goes to schedule.end_epoch, then callback(info, state).
+    After the last epoch every block is folded before any is read back.  The state is closed before the engines, whatever
+    happens.  -> (rows [n, k] of the permuted documents, topics, info); `series` names the per-epoch sums in info."""
+    n_blocks = len(ranges)
+    engines, state = [], None
+    try:
+        scales, tokens = [], []
+        for i, (a, b) in enumerate(ranges):
+            eng = new_engine()
+            engines.append(eng)
+            t, scale = setup(eng, i, a, b)
+            tokens.append(t)
+            scales.append(scale)
+        state = make_state()
+        _, acc_floats = engines[0].accumulator_device()
+        info = {"n_epochs": 0, "n_steps": 0, "rho": schedule.rhos, series: schedule.log_likelihoods, "block_ranges": ranges,
+                "permutation": perm, "tokens": tokens, "bytes_per_block_context": 3 * 4 * int(acc_floats)}
+        epoch_sum = 0.0
+        while True:
+            nxt = schedule.next_step()
+            if nxt is None:
+                break
+            _, block, rho_t = nxt
+            value = step(state, engines[block], rho_t, scales[block], want)
+            epoch_sum += value if want else float("nan")
+            if block == n_blocks - 1:
+                schedule.end_epoch(epoch_sum)
+                epoch_sum = 0.0
+                info.update(n_epochs=schedule.n_epochs_done, n_steps=schedule.n_steps)
+                if callback is not None:
+                    callback(info, state)
+        out = np.zeros((n, k), np.float32)
+        for eng in engines:
+            fold(state, eng)
+        for eng, (a, b) in zip(engines, ranges):
+            out[a:b] = rows(eng)
+        table = topics(state)
+    finally:
+        if state is not None:
+            state.close()
+        for eng in engines:
+            eng.close()
+    return out, table, dict(info, rho=list(schedule.rhos), **{series: list(schedule.log_likelihoods)})
+
+
 @_locked
 def plsa_fit_online(X, k, sample_weight=None, init="random", n_batches=64, n_epochs=5, inner_iter=3, kappa=0.7, tau0=10.0,
                     rho=None, tolerance=0.001, shuffle_documents=True, e_step_thresh=1e-32, random_state=None, device=None,
@@ -216,10 +314,7 @@ def plsa_fit_online(X, k, sample_weight=None, init="random", n_batches=64, n_epo
     info: `n_epochs`, `n_steps`, `rho` (one per step), `log_likelihoods` (L_e per epoch), `block_ranges` (row ranges of the
     permuted documents), `permutation` (None without shuffling), `tokens` (per block), `bytes_per_block_context`.
     callback(info_so_far, state) is called after every epoch.  Default arithmetic, fused schedule only."""
-    flags = resolve_flags(None)
-    if not flags & PLSA_FUSED or flags & (PLSA_REFERENCE_SUMS | PLSA_REFERENCE_LL):
-        raise ValueError("online EM runs the fused schedule in the default arithmetic only "
-                         "(ENSTOP_AMD_MATERIALISE / ENSTOP_AMD_ARITHMETIC are set)")
+    flags = plain_fused_flags("online EM")
     if not 1 <= int(n_batches) <= MAX_BATCHES:
         raise ValueError("n_batches must be in [1, %d], not %r" % (MAX_BATCHES, n_batches))
     if int(inner_iter) < 0:
@@ -233,66 +328,48 @@ def plsa_fit_online(X, k, sample_weight=None, init="random", n_batches=64, n_epo
     rng = check_random_state(random_state)
     U0, V0 = host_factors(k, init, rng, X=X)
     sw = effective_weights(sample_weight)
-    perm = rng.permutation(n) if shuffle_documents else None
-    if perm is not None:
-        X, U0 = X[perm], U0[perm]
-        sw = None if sw is None else sw[perm]
-    ranges = row_ranges_by_nnz(X.indptr, n_blocks)
-    if any(b <= a for a, b in ranges):
-        raise ValueError("plsa_fit_online: %d documents cannot be split over %d blocks" % (n, n_blocks))
-    want_ll = bool(return_info) or schedule.tolerance > 0.0
+    X, (U0, sw), perm, ranges, undo = cut_blocks("plsa_fit_online", X, n_blocks, rng, shuffle_documents, U0, sw)
     home = get_engine(device)
-    engines, state = [], None
-    try:
-        scales, tokens = [], []
-        for a, b in ranges:
-            eng = Engine(home.device)
-            engines.append(eng)
-            eng.upload_csr(X[a:b])
-            eng.set_factors(U0[a:b], V0)
-            eng.set_sample_weight(None if sw is None else sw[a:b])
-            tokens.append(block_tokens(X[a:b], None if sw is None else sw[a:b]))
-            scales.append(_scale(tokens[-1], "block %d (documents %d .. %d)" % (len(scales), a, b)))
-        state = OnlineState(home, m, k).set_topics(V0)
-        _, acc_floats = engines[0].accumulator_device()
-        info = dict(n_epochs=0, n_steps=0, rho=schedule.rhos, log_likelihoods=schedule.log_likelihoods, block_ranges=ranges,
-                    permutation=perm, tokens=tokens, bytes_per_block_context=3 * 4 * int(acc_floats))
-        epoch_ll = 0.0
-        while True:
-            step = schedule.next_step()
-            if step is None:
-                break
-            _, block, rho_t = step
-            ll = state.step(engines[block], rho_t, scales[block], inner_iter, None, e_step_thresh, want_ll, flags)
-            epoch_ll += ll if want_ll else float("nan")
-            if block == n_blocks - 1:
-                schedule.end_epoch(epoch_ll)
-                epoch_ll = 0.0
-                info.update(n_epochs=schedule.n_epochs_done, n_steps=schedule.n_steps)
-                if callback is not None:
-                    callback(info, state)
-        U = np.zeros((n, k), np.float32)
-        for eng, (a, b) in zip(engines, ranges):
-            state.fold(eng, max(int(inner_iter), 1), None, e_step_thresh, flags)
-        for eng, (a, b) in zip(engines, ranges):
-            U[a:b] = eng.get_factors(want_v=False)[0]
-        V = state.get_topics()
-    finally:
-        if state is not None:
-            state.close()
-        for eng in engines:
-            eng.close()
-    if perm is not None:
-        out = np.empty_like(U)
-        out[perm] = U
-        U = out
-    if return_info:
-        info = dict(info, rho=list(schedule.rhos), log_likelihoods=list(schedule.log_likelihoods))
-        return U, V, info
-    return U, V
+
+    def setup(eng, i, a, b):
+        sw_b = None if sw is None else sw[a:b]
+        eng.upload_csr(X[a:b])
+        eng.set_factors(U0[a:b], V0)
+        eng.set_sample_weight(sw_b)
+        tokens = block_tokens(X[a:b], sw_b)
+        return tokens, _scale(tokens, "block %d (documents %d .. %d)" % (i, a, b))
+
+    U, V, info = drive_blocks(
+        n, k, ranges, perm, schedule, bool(return_info) or schedule.tolerance > 0.0, "log_likelihoods",
+        new_engine=lambda: Engine(home.device), setup=setup, make_state=lambda: OnlineState(home, m, k).set_topics(V0),
+        step=lambda state, eng, rho_t, scale, want: state.step(eng, rho_t, scale, inner_iter, None, e_step_thresh, want, flags),
+        fold=lambda state, eng: state.fold(eng, max(int(inner_iter), 1), None, e_step_thresh, flags),
+        rows=lambda eng: eng.get_factors(want_v=False)[0], topics=lambda state: state.get_topics(), callback=callback)
+    return (undo(U), V, info) if return_info else (undo(U), V)
 
 
-class OnlinePLSA(PLSA):
+class PartialFitMixin:
+    """What the online estimators share around partial_fit's device handles (`_partial`: a state and a scratch engine)"""
+
+    def _end_partial(self):
+        p = self.__dict__.pop("_partial", None)
+        if p is not None:
+            p["state"].close()
+            p["engine"].close()
+
+    def __getstate__(self):                      # device handles do not travel: a copy starts partial_fit afresh
+        state = dict(self.__dict__)
+        state.pop("_partial", None)
+        return state
+
+    def __del__(self):
+        try:
+            self._end_partial()
+        except Exception:
+            pass
+
+
+class OnlinePLSA(PartialFitMixin, PLSA):
     """PLSA fitted by stepwise EM (plsa_fit_online; module docstring): `components_`, `embedding_`, `training_data_` as PLSA's,
     `n_iter_` = epochs run, `n_steps_` = steps taken, `online_info_` = plsa_fit_online's info.  transform, the scoring
     methods and the topic metrics are PLSA's.
@@ -333,24 +410,7 @@ class OnlinePLSA(PLSA):
         self.online_info_ = info
         return U, V, dict(n_iter=info["n_epochs"])
 
-    # -- documents in pieces -------------------------------------------------------------------------------------------
-    def _end_partial(self):
-        p = self.__dict__.pop("_partial", None)
-        if p is not None:
-            p["state"].close()
-            p["engine"].close()
-
-    def __getstate__(self):                      # device handles do not travel: a copy starts partial_fit afresh
-        state = dict(self.__dict__)
-        state.pop("_partial", None)
-        return state
-
-    def __del__(self):
-        try:
-            self._end_partial()
-        except Exception:
-            pass
-
+    # -- documents in pieces (PartialFitMixin) --------------------------------------------------------------------------
     def partial_fit(self, X, y=None, sample_weight=None):
         X = check_array(X, accept_sparse="csr")
         X = _csr(standardize_input(X))

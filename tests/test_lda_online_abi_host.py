@@ -82,25 +82,57 @@ def test_the_sources_are_build_dependencies_and_part_of_the_translation_unit():
     assert "online" not in release
 
 
+def _csrc(name):
+    return re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "enstop_amd", "csrc", name)).read())
+
+
+def _all_csrc():
+    folder = os.path.join(ROOT, "enstop_amd", "csrc")
+    return {name: _csrc(name) for name in sorted(os.listdir(folder)) if name.endswith((".hpp", ".hip"))}
+
+
 def test_the_passes_run_through_their_wrappers():
-    """no pass kernel, no stream creation, no graph call and no atomic is named in the new sources; the rounds, the tables and
-    the bound's sums are those of plsa_lda.hpp, the event discipline is plsa_online.hpp's"""
-    for name in SOURCES:
-        code = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "enstop_amd", "csrc", name)).read())
+    """no pass kernel, no stream creation, no graph call and no atomic is named in the online LDA sources or in the two host
+    sides they share code with; the round, the tables and the bound are plsa_lda.hpp's, the state frame with its event
+    discipline is plsa_online.hpp's, and each is named by the file that holds it"""
+    for name in SOURCES + ("plsa_lda.hpp", "plsa_lda_priors.hpp", "plsa_online.hpp"):
+        code = _csrc(name)
         for word in ("k_row_pass<", "k_col_pass<", "k_col_reduce_norm<", "k_loglik<", "hipStreamCreate", "hipGraph", "atomic"):
             assert word not in code, (name, word)
-    host = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "enstop_amd", "csrc", "plsa_lda_online.hpp")).read())
+    host, lda, frame = _csrc("plsa_lda_online.hpp"), _csrc("plsa_lda.hpp"), _csrc("plsa_online.hpp")
     for used in ("run_row_pass(", "run_col_pass(c, false, nullptr, thresh, 3)", "run_loglik(c, nullptr, nullptr)", "wait_ll(",
                  "StandIn u(", "run_lda_table_u(", "run_lda_table_v(", "run_lda_rows(c, alpha)", "run_lda_dirichlet<true>(",
-                 "run_lda_shift_sum(", "lda_prior_ok(", "plain_fused_refusal(", "need_factors(", "hipStreamWaitEvent(c->stream, st->ev, 0)",
-                 "hipEventRecord(st->ev, c->stream)", "plsa::k_lda_online_blend", "plsa::k_lda_topic_sums", "plsa::k_lda_wordmax",
-                 "plsa::k_lda_tables<false>"):
+                 "run_lda_shift_sum(", "lda_prior_ok(", "plsa::k_lda_topic_sums", "plsa::k_lda_wordmax", "plsa::k_lda_tables<false>"):
+        assert used in lda, used
+    for used in ("plain_fused_refusal(", "need_factors(", "hipStreamWaitEvent(c->stream, st->ev, 0)", "hipEventRecord(st->ev, c->stream)"):
+        assert used in frame, used
+    # ... and the online side reaches every one of them through the shared pieces
+    for used in ("lda_rounds(", "lda_scalar_rows(c, alpha)", "lda_bound_send(", "lda_gamma_part(c, alpha)", "lda_bound_finish(",
+                 "run_lda_topic_tables(", "online_frame_eligible(", "online_wait(st, c)", "online_record(st, c)", "online_host_wait(st)",
+                 "lda_prior_ok(", "plsa::k_lda_online_blend"):
         assert used in host, used
-    assert "run_lda_topics(" not in host and "c->cv ^= 1" not in host          # the block's own topic table stays
-    # the existing host sides are as they were: they name neither the new kernel nor the state
-    for name in ("plsa_lda.hpp", "plsa_lda_priors.hpp", "plsa_online.hpp"):
-        other = open(os.path.join(ROOT, "enstop_amd", "csrc", name)).read()
-        assert KERNEL not in other and "plsa_lda_online" not in other, name
+    # the block's own topic table stays: the online path never asks a round for the topics.  The step leaves the counts in
+    # Vacc, the fold runs no column pass; the one round writes and flips Vt under LdaColumns::TOPICS only
+    assert "run_lda_topics(" not in host and "c->cv ^= 1" not in host and "LdaColumns::TOPICS" not in host
+    step = host[host.index("int plsa_lda_online_step("):host.index("int plsa_lda_online_fold(")]
+    fold = host[host.index("int plsa_lda_online_fold("):]
+    assert step.count("LdaColumns::") == 1 and "LdaColumns::COUNTS, eta).iteration(doc_iter)" in step
+    assert fold.count("LdaColumns::") == 1 and "LdaColumns::NONE" in fold and "rounds.round(false)" in fold
+    assert "const bool topics = with_columns && columns == LdaColumns::TOPICS;" in lda
+    assert "if (topics) CHK(run_lda_topics(c, eta));" in lda and "if (topics) { c->cv ^= 1; l.b_valid = false; }" in lda
+    assert lda.count("c->cv ^= 1") == 1 and lda.count("run_lda_topics(") == 2          # (its definition and the round)
+    # the send precedes the global update, the wait follows it
+    assert step.index("lda_bound_send(") < step.index("lda_online_global_update(") < step.index("online_record(") \
+        < step.index("lda_bound_finish(")
+    # one site each in the tree: the event wait and record on the block's stream, the round, the topic-side chain, and the
+    # launches of the kernels that belong to one feature
+    tree = _all_csrc()
+    for once in ("hipStreamWaitEvent(c->stream, st->ev, 0)", "hipEventRecord(st->ev, c->stream)", "int round(bool",
+                 "plsa::k_lda_topic_sums,", "plsa::k_lda_topic_partial,", "plsa::k_lda_wordmax,", "plsa::k_lda_tables<false>,",
+                 "plsa::" + KERNEL + ",", "plsa::k_lda_rows_v,", "plsa::k_lda_bound_v,"):
+        assert sum(code.count(once) for code in tree.values()) == 1, once
+    assert "int round(bool" in lda and "plsa::" + KERNEL + "," in host
+    assert "plsa::k_lda_rows_v," in tree["plsa_lda_priors.hpp"] and "plsa::k_lda_bound_v," in tree["plsa_lda_priors.hpp"]
 
 
 def test_the_documents_and_the_package_name_them():

@@ -79,7 +79,13 @@ def test_the_kernel_takes_its_indices_from_the_plan():
         assert used in topic, used
     host = _code("plsa_lda_online.hpp")
     assert "dim3(plsa::plan::blend_grid(st->m)), dim3(plsa::plan::BLEND_BLOCK)" in host
-    assert "plsa::plan::lda_bound_grid(st->m)" in host
+    # the topic-side chain is plsa_lda.hpp's, on the side it is handed: the slab count of the state's m
+    shared = _code("plsa_lda.hpp")
+    chain = shared[shared.index("int run_lda_topic_tables("):shared.index("int run_lda_table_v(")]
+    assert "plsa::plan::lda_bound_grid(t.m)" in chain and "st->m, st->k, st->kp}" in host
     # the sweep of k_lda_topic_partial is launched for a lambda the host set, never behind the blend
+    assert chain.index("if (sweep) {") < chain.index("plsa::k_lda_topic_partial") < chain.index("plsa::k_lda_topic_sums")
     update = host[host.index("int lda_online_global_update("):host.index("struct LdaOnlineTopicSide")]
-    assert "lda_online_tables(st, c, false)" in update and "k_lda_topic_partial" not in update
+    assert "run_lda_topic_tables(c, lda_online_side(st), false, true)" in update and "k_lda_topic_partial" not in update
+    set_lambda = host[host.index("int plsa_lda_online_set_lambda("):host.index("int plsa_lda_online_get_lambda(")]
+    assert "run_lda_topic_tables(h, lda_online_side(st), true, true)" in set_lambda

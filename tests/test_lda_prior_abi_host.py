@@ -90,14 +90,25 @@ def test_the_passes_run_through_their_wrappers():
         if name in ("plsa_lda_prior_plan.hpp", "plsa_lda_prior_math.hpp"):
             assert "hip" not in code.replace("__HIPCC__", "").lower(), name
     host = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "enstop_amd", "csrc", "plsa_lda_priors.hpp")).read())
-    for used in ("run_row_pass(", "run_col_pass(c, false, nullptr, thresh, 3)", "run_loglik(", "plsa::k_ll_final", "StandIn u(",
-                 "plsa::fit::REFIT", "lda_context_ok(", "lda_eligible(", "fit_open(", "fit_run(", "run_lda_table_u(", "run_lda_table_v(",
-                 "plsa::lda::maximise_alpha(", "plsa::lda::maximise_eta(", "plsa::plan::prior_due("):
+    for used in ("plsa::k_ll_final", "plsa::fit::REFIT", "lda_context_ok(", "lda_eligible(", "fit_open(", "fit_run(", "run_lda_table_u(",
+                 "run_lda_table_v(", "plsa::lda::maximise_alpha(", "plsa::lda::maximise_eta(", "plsa::plan::prior_due(",
+                 # the round and the bound are plsa_lda.hpp's, entered with the vector forms of the rows step and of gamma's part
+                 "lda_rounds(c, thresh, [this] { return run_lda_rows_v(c); }", "lda_bound_send(c, \"plsa_lda_prior_bound\", [c] { return run_lda_dirichlet_v(c); }",
+                 "lda_bound_finish(c, lgamma(sum) - each,"):
         assert used in host, used
-    # the scalar entry points' host side is as it was: it names none of the new kernels
-    scalar = open(os.path.join(ROOT, "enstop_amd", "csrc", "plsa_lda.hpp")).read()
+    assert "int round(" not in host and "int iteration()" in host
+    scalar = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "enstop_amd", "csrc", "plsa_lda.hpp")).read())
+    for used in ("run_row_pass(", "run_col_pass(c, false, nullptr, thresh, 3)", "run_loglik(", "StandIn u(", "run_lda_table_u(",
+                 "run_lda_table_v(", "CHK(rows());", "CHK(gamma_part());"):
+        assert used in scalar, used
+    # the scalar entry points' host side names none of the new kernels: each is launched from one place, this feature's
+    folder = os.path.join(ROOT, "enstop_amd", "csrc")
     for kernel in KERNELS:
         assert kernel not in scalar, kernel
+        sites = [name for name in sorted(os.listdir(folder))
+                 for _ in range(re.sub(r"//[^\n]*", "", open(os.path.join(folder, name)).read()).count("plsa::" + kernel))]
+        assert set(sites) == {"plsa_lda_priors.hpp"}, (kernel, sites)
+        assert len(sites) == 1 or kernel == "k_lda_logmean", (kernel, sites)          # (a prefix of k_lda_logmean_sums)
 
 
 def test_the_documents_and_the_package_name_them():

@@ -95,6 +95,12 @@ def test_the_step_runs_the_existing_passes_and_normalisation_through_their_wrapp
             assert kernel not in code, (name, kernel)
     host = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "enstop_amd", "csrc", "plsa_online.hpp")).read())
     assert "plsa::k_colsum_final" in host and "plsa::k_v_normalise" in host and "plsa::k_online_blend" in host
+    # the state frame (shared with online LDA) lives here: the event wait and record on the block's stream, once each in the tree
+    folder = os.path.join(ROOT, "enstop_amd", "csrc")
+    tree = "".join(open(os.path.join(folder, name)).read() for name in sorted(os.listdir(folder)))
+    for once in ("hipStreamWaitEvent(c->stream, st->ev, 0)", "hipEventRecord(st->ev, c->stream)", "struct OnlineFrame {"):
+        assert once in host and tree.count(once) == 1, once
+    assert "struct plsa_online : OnlineFrame {" in host
 
 
 def test_the_package_exports_the_online_module():
